@@ -2,11 +2,17 @@
 """bench.py — throughput of the batched offline render hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload c2|t1|c3|c5] [--instances I] [--seconds S]
+                    [--dump-outputs DIR] [--full]
 
 A "step" = one start_rendering_sync-equivalent pass over one batch of synthetic input:
 `instances` independent OfflineAudioContexts x `seconds` s @ 48 kHz stereo, inputs already
 resident in HBM (white noise generated on the device).  Default workload = BASELINE.json
 configs[1] (C2): 1024 contexts, BufferSource -> Biquad(lowpass 200 Hz, Q 1) -> Gain(0.5) -> destination.
+
+A plain run times the headline only: set-up (graded arena, batch, first render), warm-up, the K timed
+steps, the outputs of the last step if --dump-outputs is given, the result line.  --full adds everything
+else the line used to carry: the `cold` and `sustained` records, the T1 / C3 / C4 / ... riders, their HBM
+traffic measured by rocprofv3 child runs, the `e2e` record, the CPU baselines and the detail file.
 
 N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ...`, one rank per GPU;
 independent batches shard over the GPUs with no data-path collective (weak scaling: every GPU
@@ -340,12 +346,45 @@ F64_WORKLOADS = ("c2", "c2k", "c1a", "t1", "c4", "fbq", "pluck", "osc")
 
 PREROLL_S = 0.15
 
+# --dump-outputs: at most this many bytes of .npy files in all, the sampled contexts drawn with this seed
+DUMP_BYTES = 64 * 10**6
+DUMP_SEED = 0xD1F
 
-def measure(torch, waa, hip, name, n_inst, seconds, steps, warmup, rank, world, local_rank, dist, backend, sustain_s=0.0):
+
+def dump_outputs(ctx, out_dir, bins=None):
+    """What a caller of the timed path receives from its last step, as float32 .npy files under `out_dir`, for a fixed sample of
+    the batch's contexts (seeded, sorted): `output.npy`, their rendered AudioBuffers [contexts, channels, frames] (every frame,
+    unless one context alone exceeds the budget: then a seeded sorted sample of frames too), and for C4 `analyser_db.npy`,
+    their rows of the batched analyser pull.  The whole batch is GBs; the files stay under DUMP_BYTES in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES - 4096  # (room for the .npy headers)
+    n_inst, nch, frames = ctx.n_instances, ctx.number_of_channels, ctx.length
+    row = 0 if bins is None else bins.shape[1] * 4
+    rng = np.random.default_rng(DUMP_SEED)
+    k = int(min(n_inst, max(1, budget // (nch * frames * 4 + row))))
+    insts = np.sort(rng.choice(n_inst, size=k, replace=False))
+    if bins is not None:
+        np.save(os.path.join(out_dir, "analyser_db.npy"), np.ascontiguousarray(bins[insts], np.float32))
+    keep = int(min(frames, (budget - k * row) // (k * nch * 4)))
+    cols = None if keep == frames else np.sort(rng.choice(frames, size=keep, replace=False))
+    out = np.empty((k, nch, keep), np.float32)
+    chan = np.empty(frames, np.float32)
+    fp = chan.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    for j, inst in enumerate(insts):
+        for c in range(nch):
+            ctx._b.check(ctx._b.download(ctx._handle, int(inst), c, fp, frames))
+            out[j, c] = chan if cols is None else chan[cols]
+    np.save(os.path.join(out_dir, "output.npy"), out)
+
+
+def measure(torch, waa, hip, name, n_inst, seconds, steps, warmup, rank, world, local_rank, dist, backend, sustain_s=0.0,
+            preroll_s=None, dump_dir=None):
     """One workload on this rank's GPU: build (untimed), first render = plan + allocation + render (first_render_ms, what a
     caller of an offline context really waits for; plan_ms = its host part), then the bench protocol (W untimed + K timed
     steps, barrier + sync on both sides, MAX over ranks).  C4's step includes the batched analyser pull (one
-    get_float_frequency_data per context).  Returns the full record (rank 0 compacts it)."""
+    get_float_frequency_data per context).  Without a sustained record, `preroll_s` seconds of untimed steps (default
+    PREROLL_S) go in front of the protocol.  `dump_dir`: the last timed step's outputs are written there (dump_outputs).
+    Returns the full record (rank 0 compacts it)."""
     frames = int(round(seconds * SR))
     nq = (frames + RQ - 1) // RQ
     gen = torch.Generator(device="cuda")
@@ -375,6 +414,7 @@ def measure(torch, waa, hip, name, n_inst, seconds, steps, warmup, rank, world, 
     timing = head.split("| timing: ", 1)[1] if "| timing: " in head else None
     dev_t = lambda v: torch.tensor([v], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")  # noqa: E731
     sustained = None
+    preroll_s = PREROLL_S if preroll_s is None else preroll_s
     if sustain_s > 0:
         # K x 1.4 ms is a 30 ms window: too short to be seen by an outside sampler and sensitive to one slow launch.  The same
         # protocol (barrier + sync on both sides, MAX over ranks) over enough steps to fill >= sustain_s seconds; `value` stays
@@ -387,10 +427,11 @@ def measure(torch, waa, hip, name, n_inst, seconds, steps, warmup, rank, world, 
         sus_elapsed = timed_steps(step, torch.cuda.synchronize, n_sus, 0, dist=dist, device_tensor=dev_t)
         sustained = {"steps": n_sus, "seconds": round(sus_elapsed, 4), "ms_per_step": sus_elapsed / n_sus * 1e3,
                      "value": world * n_inst * nq * n_sus / sus_elapsed, "order": "before the K timed steps"}
-    elif PREROLL_S > 0:
-        # (the riders: 0.15 s of untimed back-to-back steps for the same reason)
+    elif preroll_s > 0:
+        # (the riders: 0.15 s of untimed back-to-back steps for the same reason; a plain run's headline: as long as the
+        # sustained record of a --full run takes, so that both time the K steps from the same state)
         t_pre = time.perf_counter()
-        while time.perf_counter() - t_pre < PREROLL_S:
+        while time.perf_counter() - t_pre < preroll_s:
             step()
             torch.cuda.synchronize()  # (per step: 0.15 s of DEVICE time, not 0.15 s worth of queued launches)
     ctx.profile(True)
@@ -398,6 +439,8 @@ def measure(torch, waa, hip, name, n_inst, seconds, steps, warmup, rank, world, 
     elapsed = timed_steps(step, torch.cuda.synchronize, steps, warmup, dist=dist, device_tensor=dev_t,
                           after_warmup=ctx.profile_reset)
     ctx.sync()
+    if dump_dir is not None:
+        dump_outputs(ctx, dump_dir, bins)
     prof = sorted(ctx.profile_entries(), key=lambda e: -e[2])
     ctx.close()
     del noise
@@ -677,7 +720,8 @@ def main():
     ap.add_argument("--instances", type=int, default=None, help="contexts per GPU")
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--sustain", type=float, default=0.6,
-                    help="seconds of back-to-back steps timed AFTER the K-step protocol for the `sustained` record (0 = off)")
+                    help="seconds of back-to-back steps timed before the K-step protocol for the `sustained` record (--full; 0 = off); "
+                         "a plain run steps as long untimed")
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="do not measure the headline's HBM traffic in this run (two rocprofv3 --pmc child runs, ~30 s): replay the stamped record")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -687,7 +731,13 @@ def main():
     ap.add_argument("--no-preroll", action="store_true",
                     help="no untimed back-to-back steps in front of the W + K protocol (the profiled child runs: every kernel exactly 5 times)")
     ap.add_argument("--no-extra", action="store_true", help="only the headline workload: no T1 / C3 / C4 / ... records, no e2e record")
-    ap.add_argument("--detail", default=None, help="file for the full per-workload records (default: gpurun_out/bench_detail.json)")
+    ap.add_argument("--detail", default=None, help="file for the full per-workload records (default with --full: out/bench_detail.json)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline too: the `cold` and `sustained` records, the riders (T1 / C3 / C4 / ... "
+                         "of the default workload), their live PMC traffic, the `e2e` record, the CPU baselines, the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step rendered as DIR/<name>.npy (float32; a fixed, seeded "
+                         "sample of the contexts, at most 64 MB in all)")
     ap.add_argument("--arena-gb", type=int, default=int(os.environ.get("WAA_BENCH_ARENA_GB", "64")),
                     help="GiB of graded device arena reserved before the first batch (waa_device_arena_reserve_graded: what a serving "
                          "process does at start-up); 0 = plain hipMalloc for everything, the form rounds 1-5 measured")
@@ -744,7 +794,7 @@ def main():
     arena = None
     share_gpu = os.environ.get("WAA_BENCH_SHARE_GPU") == "1"
     if args.arena_gb > 0 and not share_gpu:
-        if name == "c2" and args.instances is None and args.seconds == 10.0 and not args.no_cold:
+        if args.full and name == "c2" and args.instances is None and args.seconds == 10.0 and not args.no_cold:
             try:
                 c = measure(torch, waa, hip, name, n_inst, args.seconds, max(3, args.steps // 2), 1, rank, world, local_rank, dist, backend)
                 cold = {"ms_per_step": round(c["ms_per_step"], 4), "kernel_ms": round(c["roofline"]["kernel_ms_per_step"], 4),
@@ -768,13 +818,15 @@ def main():
         except Exception as e:  # the arena is an optimisation: without it everything is served by hipMalloc as before
             arena = {"error": repr(e)[:160]}
     rec = measure(torch, waa, hip, name, n_inst, args.seconds, args.steps, args.warmup, rank, world, local_rank, dist,
-                  backend, sustain_s=args.sustain)
+                  backend, sustain_s=args.sustain if args.full else 0.0,
+                  preroll_s=None if args.full else 0.0 if args.no_preroll else max(PREROLL_S, args.sustain),
+                  dump_dir=args.dump_outputs if rank == 0 else None)
     # The north-star target graph (T1) and the other BASELINE configs ride along in the same line (compact: the driver
     # keeps about 4 KB of it; the full records go to the detail file), so that one driver run verifies them all: every
     # rank renders them (same barrier protocol), rank 0 reports.  Fewer steps each.  With N > 1 only T1 and C4 (the
     # config BASELINE.json shards over 8 GPUs: 4096 contexts = 512 per GPU) ride along.
     extra = {}
-    default_run = name == "c2" and args.instances is None and args.seconds == 10.0 and not args.no_extra
+    default_run = args.full and name == "c2" and args.instances is None and args.seconds == 10.0 and not args.no_extra
     if default_run:
         subs = ("t1", "c3", "c4", "c5", "c1a", "os2", "hrtf", "echo") if world == 1 else ("t1", "c4")
         for sub in subs:
@@ -886,7 +938,7 @@ def main():
                 out["roofline"][k] = roof[k]
         detail = {"headline": rec, "workloads": extra, "e2e": e2e, "box": detail_box}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline(waa, name, int(round(args.seconds * SR)))
             except Exception as e:  # the baseline is reporting only; never fail the bench line on it
@@ -927,14 +979,15 @@ def main():
                 out["configs"]["c4"]["contexts_per_gpu"] = extra["c4"]["config"]["contexts_per_gpu"]
         if e2e is not None:
             out["e2e"] = {k: (round(v, 2) if isinstance(v, float) else v) for k, v in e2e.items() if k != "note"}
-        path = args.detail or os.path.join(ROOT, "gpurun_out", "bench_detail.json")
-        try:
-            os.makedirs(os.path.dirname(path), exist_ok=True)
-            with open(path, "w") as f:
-                json.dump(detail, f, indent=1)
-            out["detail_file"] = os.path.relpath(path, ROOT)
-        except OSError:
-            pass
+        if args.full or args.detail:
+            path = args.detail or os.path.join(ROOT, "out", "bench_detail.json")
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                with open(path, "w") as f:
+                    json.dump(detail, f, indent=1)
+                out["detail_file"] = os.path.relpath(path, ROOT)
+            except OSError:
+                pass
         # The driver keeps the contract's keys and the LAST 2000 characters of the line: what a reader of the driver's record should see
         # of the riders goes last — the north-star graph's record, then what one start_rendering_sync costs
         for k in ("t1", "one_shot"):

@@ -14,23 +14,58 @@ REF = "/root/reference"
 PATCH = os.path.join(ROOT, "shim", "reference.patch")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF) or shutil.which("patch") is None, reason="no reference tree / patch(1) here")
+# every processor SURVEY section 8 names reports itself to the shim
+_PROCESSORS = (("gain", "GainRenderer"), ("biquad_filter", "BiquadFilterRenderer"), ("convolver", "ConvolverRenderer"),
+               ("stereo_panner", "StereoPannerRenderer"), ("panner", "PannerRenderer"), ("analyser", "AnalyserRenderer"),
+               ("waveshaper", "WaveShaperRenderer"), ("audio_buffer_source", "AudioBufferSourceRenderer"),
+               ("iir_filter", "IirFilterRenderer"), ("oscillator", "OscillatorRenderer"), ("constant_source", "ConstantSourceRenderer"),
+               ("delay", "DelayWriter"), ("delay", "DelayReader"), ("destination", "DestinationRenderer"))
+
+
+def _post_images(patch_text):
+    """{path: [post-image of each hunk]} of a unified diff: context and added lines, in order (a file the patch creates is
+    its one hunk's post-image)"""
+    out, path, hunk = {}, None, None
+    for line in patch_text.splitlines(keepends=True):
+        if line.startswith("diff "):
+            path = hunk = None
+        elif line.startswith("+++ "):
+            path = line[4:].split("\t")[0].strip()
+            path = path[2:] if path.startswith("b/") else path
+        elif line.startswith("@@") and path is not None:
+            hunk = []
+            out.setdefault(path, []).append(hunk)
+        elif hunk is not None and line[:1] in (" ", "+"):
+            hunk.append(line[1:])
+        elif hunk is not None and line.startswith("\\") and hunk:
+            hunk[-1] = hunk[-1].rstrip("\n")  # "\ No newline at end of file"
+    return {p: ["".join(h) for h in hs] for p, hs in out.items()}
+
+
+def _gpu_desc_in_front_of_process(src, proc):
+    body = src[src.index(f"impl AudioProcessor for {proc}"):]
+    return "fn gpu_desc(&self)" in body[:body.index("fn process(")]
+
+
 def test_patch_applies_and_carries_the_module_files(tmp_path):
+    """what the patch itself says (the module files it adds are shim/src/gpu/*, every processor's `gpu_desc` lands in front of
+    its `process`) and, where the reference tree it was cut from exists, that it applies there and the patched tree says the same"""
+    post = _post_images(open(PATCH).read())
+    for f in ("mod.rs", "ffi.rs"):
+        assert post[f"src/gpu/{f}"] == [open(os.path.join(ROOT, "shim", "src", "gpu", f)).read()], f
+    for node, proc in _PROCESSORS:
+        hunks = [h for h in post.get(f"src/node/{node}.rs", []) if f"impl AudioProcessor for {proc}" in h]
+        assert hunks and all(_gpu_desc_in_front_of_process(h, proc) for h in hunks), (node, proc)
+    if not os.path.isdir(REF) or shutil.which("patch") is None:
+        return
     tree = tmp_path / "crate"
     shutil.copytree(REF, tree, ignore=shutil.ignore_patterns("target", ".git"))
     r = subprocess.run(["patch", "-p1", "-s", "-i", PATCH], cwd=tree, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     for f in ("mod.rs", "ffi.rs"):
         assert open(tree / "src" / "gpu" / f).read() == open(os.path.join(ROOT, "shim", "src", "gpu", f)).read(), f
-    # every processor SURVEY section 8 names reports itself to the shim
-    for node, proc in (("gain", "GainRenderer"), ("biquad_filter", "BiquadFilterRenderer"), ("convolver", "ConvolverRenderer"),
-                       ("stereo_panner", "StereoPannerRenderer"), ("panner", "PannerRenderer"), ("analyser", "AnalyserRenderer"),
-                       ("waveshaper", "WaveShaperRenderer"), ("audio_buffer_source", "AudioBufferSourceRenderer"),
-                       ("iir_filter", "IirFilterRenderer"), ("oscillator", "OscillatorRenderer"), ("constant_source", "ConstantSourceRenderer"),
-                       ("delay", "DelayWriter"), ("delay", "DelayReader"), ("destination", "DestinationRenderer")):
-        src = open(tree / "src" / "node" / f"{node}.rs").read()
-        body = src[src.index(f"impl AudioProcessor for {proc}"):]
-        assert "fn gpu_desc(&self)" in body[:body.index("fn process(")], (node, proc)
+    for node, proc in _PROCESSORS:
+        assert _gpu_desc_in_front_of_process(open(tree / "src" / "node" / f"{node}.rs").read(), proc), (node, proc)
 
 
 # ---- declarations: count AND type of every parameter, return type, struct layouts, constants ------------------------------------

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""tools/pmc_merge.py <workload> <contexts> <frames> <tag> — fold gpurun_out/<tag>_{stats,fetch,write}.txt (tools/pmc_pass.sh)
+"""tools/pmc_merge.py <workload> <contexts> <frames> <tag> — fold $WAA_OUT_DIR/<tag>_{stats,fetch,write}.txt (tools/pmc_pass.sh; default out/)
 into profiles/pmc_traffic.json: HBM bytes per launch of every product kernel (FETCH_SIZE x 2, the gfx950 correction of
 MI355X_MICROARCH.md for wide coalesced reads, + WRITE_SIZE; both counters are in KiB... rocprofv3 reports them in KB of
 1024 B) and per render step (sum over kernels x launches per step)."""
@@ -10,6 +10,7 @@ import sys
 
 name, contexts, frames, tag = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+out_dir = os.path.join(root, os.environ.get("WAA_OUT_DIR", "out"))
 
 
 def parse(path):
@@ -34,9 +35,9 @@ def short(k):
     return m.group(2) if m else k
 
 
-stats, _ = parse(os.path.join(root, "gpurun_out", f"{tag}_stats.txt"))
-_, fetch = parse(os.path.join(root, "gpurun_out", f"{tag}_fetch.txt"))
-_, write = parse(os.path.join(root, "gpurun_out", f"{tag}_write.txt"))
+stats, _ = parse(os.path.join(out_dir, f"{tag}_stats.txt"))
+_, fetch = parse(os.path.join(out_dir, f"{tag}_fetch.txt"))
+_, write = parse(os.path.join(out_dir, f"{tag}_write.txt"))
 steps = 4  # --steps 3 --warmup 1 (+ the planning render: 5 launches of every per-step kernel)
 kernels, total = {}, 0.0
 for k, (n_calls, avg_us) in stats.items():
