@@ -65,3 +65,27 @@ def _compare_all(orc, out, build, chunk, max_abs):
     return worst_rms, worst_abs
 
 
+
+
+def _rerender_bit_identical(ctx, out):
+    """out: the batch's FIRST render [n_inst, channels, frames], downloaded.  Renders the batch again (the bench's timed step: only
+    the buffers the planner registered are reset in front of it), downloads it one instance at a time (waa_download: host memory
+    stays at one copy of the batch) and compares it with `out` bit for bit, as u32 (NaNs compare too).  `out` holds the second
+    render afterwards."""
+    n_inst, nch, frames = out.shape
+    ctx.render_async()
+    ctx.sync()
+    row = np.empty((nch, frames), np.float32)
+    bad, first = 0, None
+    for i in range(n_inst):
+        for c in range(nch):
+            ctx._b.check(ctx._b.download(ctx._handle, i, c, row[c].ctypes.data_as(ctypes.POINTER(ctypes.c_float)), frames))
+        diff = row.view(np.uint32) != out[i].view(np.uint32)
+        if diff.any():
+            if first is None:
+                c, f = np.unravel_index(int(np.argmax(diff)), diff.shape)
+                first = (i, int(c), int(f), float(out[i, c, f]), float(row[c, f]))
+            bad += 1
+        out[i] = row
+    assert bad == 0, (f"the second render differs from the first in {bad} of {n_inst} instances; the first difference at "
+                      f"(instance, channel, frame) {first[:3]}: {first[3]!r} then {first[4]!r}")
