@@ -364,6 +364,9 @@ waa_status waa_disconnect(waa_batch* batch, uint32_t from, uint32_t from_output,
  * waa_batch_rearm, waa_source_set_buffer_batch / waa_source_set_buffer_pcm16_batch upload INTO the device buffers the batch was
  * planned with (same channels, frames and rate: anything else is an InvalidStateError), waa_source_adopt_device accepts the
  * pointer it already reads, and waa_render renders from the initial state.  Everything else of the batch is frozen as before.
+ * A batch whose plan holds values rendered from the graph at plan time — an AudioBufferSourceNode's playbackRate / detune or a
+ * PannerNode's position / orientation with an input from the graph, resolved per quantum when the batch is planned — cannot be
+ * re-armed (InvalidStateError): new audio may change those values, and re-arming neither plans nor allocates.
  * waa_render_sharded does this for the sub-batches of a job when waa_sharded_job.reuse_batches is set. */
 waa_status waa_batch_rearm(waa_batch* batch);
 waa_status waa_sync(waa_batch* batch);
@@ -414,7 +417,9 @@ typedef struct waa_sharded_job {
   void* user;
   uint32_t reuse_batches;        /* 1: `setup` configures every sub-batch the same way (nothing depends on `first`): a sub-batch that
                                   * has been downloaded is re-armed (waa_batch_rearm) for a later sub-batch of the same size instead
-                                  * of being destroyed — the later one skips creation, setup and planning */
+                                  * of being destroyed — the later one skips creation, setup and planning.  Ignored (every
+                                  * sub-batch is created anew) when the graph has an edge into an AudioParam: its plan may hold
+                                  * values rendered from the sub-batch's own audio (waa_batch_rearm) */
 } waa_sharded_job;
 /* Blocks until every context is rendered and downloaded; *seconds (may be NULL) = wall time.  Pinned host buffers let
  * the transfers run at link speed, and a device arena (waa_device_arena_reserve, once per process) keeps hipMalloc / hipFree —

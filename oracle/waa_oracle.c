@@ -3868,7 +3868,9 @@ waa_status orc_set_threads(orc_batch* b, int32_t n) {
 }
 
 /* waa_batch_rearm: the product library's "same graph, new audio" entry point.  The interpreter has no plan to keep: a batch is put
- * back in front of its render (orc_rewind's state reset) and then takes new source buffers like a fresh one. */
+ * back in front of its render (orc_rewind's state reset) and then takes new source buffers like a fresh one.  Unlike the product,
+ * it accepts a graph whose source playbackRate / detune or panner position is driven from the graph: it renders those params anew
+ * on every render, where the product's plan holds the values rendered at plan time and refuses the re-arm. */
 waa_status orc_rewind(orc_batch* b);
 waa_status orc_batch_rearm(orc_batch* b) {
   if (!b) return fail(WAA_ERR_INVALID_ARGUMENT, "null batch");

@@ -23,10 +23,14 @@ LATE_STARTS = True
 FRAMES = int(os.environ.get("FUZZ_FRAMES", 2048 * 5 + 200))   # (FUZZ_FRAMES / FUZZ_INST: campaign variants, tools/fuzz_campaign.py)
 
 
-def build_random_graph(be, seed, frozen=False, tap=None):
+def build_random_graph(be, seed, frozen=False, tap=None, audio=None):
     """frozen: WaveShapers may oversample (2x / 4x) and PannerNodes may use the HRTF model (extra draws: other graphs
     than the same seed without it).  tap = k (debugging aid, tools/fuzz_tap_probe.py): the SAME graph, but only node k of
-    its node list feeds the destination — where along the graph does a difference start?"""
+    its node list feeds the destination — where along the graph does a difference start?  audio(n_inst, n_ch, length, seed0)
+    -> [n_inst, n_ch, length] f32: the audio of the batch-filled BufferSources (default white_noise); the generator makes the
+    same draws with any of them, so a seed builds the same graph on other audio (tests/test_rearm.py)."""
+    if audio is None:
+        audio = white_noise
     rng = np.random.default_rng(seed if not frozen else seed + 100000)
     # FUZZ_MIXED_COUNTS=1 (campaign variant): one instance of some buffer sources plays an AudioBuffer of another channel
     # count (own generator: the graphs of a seed stay what they are without the switch)
@@ -52,7 +56,7 @@ def build_random_graph(be, seed, frozen=False, tap=None):
                 nch = int(wide_rng.choice([1, 2, 4, 6, 8]))
             n = c.create_buffer_source()
             length = FRAMES if rng.random() < 0.7 else int(rng.integers(300, FRAMES // 2))  # some end early
-            n.set_buffer_batch(white_noise(N_INST, nch, length, seed0=int(rng.integers(1, 1 << 20))) * 0.5, SR)
+            n.set_buffer_batch(audio(N_INST, nch, length, seed0=int(rng.integers(1, 1 << 20))) * 0.5, SR)
             if mix_rng is not None and mix_rng.random() < 0.4:
                 other = int(mix_rng.choice([k for k in (1, 2, 4) if k != nch]))
                 n.set_buffer(waa.AudioBuffer(white_noise(1, other, length, seed0=int(mix_rng.integers(1, 1 << 20)))[0] * 0.5, SR),

@@ -9,7 +9,9 @@ import numpy as np
 import pytest
 
 import web_audio_api_rs_amd as waa
+from bench_workloads import load_bench
 from graphs import c2, rms_err, white_noise
+from rearm import assert_same_bits, modulated_graph, sparsify
 from web_audio_api_rs_amd.sharding import plan_shards, render_sharded
 
 RQ = 128
@@ -407,17 +409,78 @@ def test_rearmed_batch_renders_new_audio_without_a_new_plan(hip, orc):
     assert np.array_equal(second, want) and not np.array_equal(second, first)
 
 
+def _reuse_case(hip, graph, n, frames):
+    """(build, host_in, host_out, render_sharded keywords, bins or None) of a sharded job of `graph`: the existing Biquad + Gain
+    graph, bench.build_workload's c2 / c4 / t1 as bench.py's e2e record runs them, or a graph whose streamed source drives a
+    second source's playbackRate and a panner's position (rendered at plan time: its sub-batches must not be re-armed).  The
+    contexts' audio changes from sub-batch to sub-batch: noise, and in every other block of four contexts the sparse pattern
+    (tests/rearm.py)"""
+    noise = white_noise(n, 2, frames, seed0=0x5B0)
+    for lo in range(4, n, 8):
+        noise[lo:lo + 4] = sparsify(noise[lo:lo + 4])
+    kw, bins = {}, None
+    if graph == "biquad_gain":
+        build = _build(hip)
+    elif graph == "modulated":
+        def build(k, device):
+            return modulated_graph(hip, k, frames, ("playback_rate", "position_x"), "source", device=device)
+    else:
+        bench = load_bench()
+        name = graph.split("_")[0]
+
+        def build(k, device):
+            return bench.build_workload(waa, hip, name, k, frames, device, None)
+        if name == "c4":
+            bins = np.zeros((n, 1024), np.float32)
+
+            def pull(ctx, lo, hi):
+                an = next(nd for nd in ctx._nodes if isinstance(nd, waa.AnalyserNode))
+                an.get_float_frequency_data_all(out=bins[lo:hi])
+            kw["pull"] = pull
+    host_in = noise
+    if "pcm_in" in graph:
+        host_in = np.ascontiguousarray(np.round(np.transpose(noise, (0, 2, 1)) * 32767.0).astype(np.int16))
+        kw["pcm16"] = True
+    if graph.endswith("pcm_in_out"):
+        kw["out_pcm16"] = True
+        host_out = np.zeros((n, frames, 2), np.int16)
+    else:
+        host_out = np.zeros((n, 2, frames), np.float32)
+    return build, host_in, host_out, kw, bins
+
+
 @pytest.mark.gpu
-def test_sharded_render_with_reused_batches_equals_the_plain_pipeline(hip):
-    """waa_sharded_job.reuse_batches: later sub-batches of the same size re-arm a downloaded one — same bits"""
-    n, frames = 32, RQ * 30 + 5
-    noise = white_noise(n, 2, frames)
-    outs = []
+@pytest.mark.parametrize("graph", ["biquad_gain", "c2_pcm_in", "c2_pcm_in_out", "c4_pull", "t1", "modulated"])
+def test_sharded_render_with_reused_batches_equals_the_plain_pipeline(hip, graph):
+    """waa_sharded_job.reuse_batches: later sub-batches of the same size re-arm a downloaded one — same bits.  8 sub-batches of 4
+    contexts on one device, 4 in flight: with reuse at least 4 of them are re-armed (build() runs once for the template and once
+    per sub-batch the library creates) — except for a graph whose plan holds values rendered from a sub-batch's own audio, which
+    is never re-armed (1 + 8 calls)"""
+    n = 32
+    frames = RQ * 30 + 5 if graph == "biquad_gain" else RQ * 60 + 5
+    outs, bins, calls = [], [], []
     for reuse in (False, True):
-        out = np.zeros((n, 2, frames), np.float32)
-        render_sharded(_build(hip), noise, out, devices=[0], sub_batches=8, reuse=reuse)
+        build, host_in, out, kw, b = _reuse_case(hip, graph, n, frames)
+        count = [0]
+
+        def counted(k, device, build=build, count=count):
+            count[0] += 1
+            return build(k, device)
+        render_sharded(counted, host_in, out, devices=[0], sub_batches=8, reuse=reuse, **kw)
         outs.append(out)
-    assert np.array_equal(outs[0], outs[1]) and np.abs(outs[0]).max() > 1e-3
+        bins.append(b)
+        calls.append(count[0])
+    assert_same_bits(outs[1], outs[0], f"{graph}: the sharded render with re-used sub-batches",
+                     axes=("context", "frame", "channel") if graph.endswith("pcm_in_out") else ("context", "channel", "frame"))
+    if bins[0] is not None:
+        assert_same_bits(bins[1], bins[0], f"{graph}: the analyser pull of re-used sub-batches", axes=("context", "bin"))
+        assert np.isfinite(bins[0]).any()
+    assert np.abs(outs[0].astype(np.float32)).max() > 1e-3
+    assert calls[0] == 1 + 8
+    if graph == "modulated":
+        assert calls[1] == 1 + 8, calls
+    else:
+        assert calls[1] <= 1 + 4, calls
 
 
 def test_sharded_render_reuse_flag_on_the_oracle(orc):

@@ -1231,10 +1231,17 @@ waa_status waa_plan_describe(waa_batch* b, char* buf, size_t cap, size_t* needed
 // A serving loop renders the same graph over and over with new audio: the batch keeps its plan, its device buffers and its tables;
 // waa_source_set_buffer_batch / _pcm16_batch / waa_source_adopt_device then REFILL the source buffers of the shape the batch was
 // planned with (anything else is an InvalidStateError), and waa_render renders from the initial state as every render does.
+// A plan that holds values rendered from the graph at plan time (resolve_source_rate_modulation: a source's playbackRate / detune
+// or a panner's position / orientation driven from the graph) is refused: those values came from the old audio, and re-planning
+// here would break the promise of no plan and no allocation.
 waa_status waa_batch_rearm(waa_batch* b) {
   if (!b) return fail(WAA_ERR_INVALID_ARGUMENT, "null batch");
   if (b->dry) return fail(WAA_ERR_DEVICE, "plan-only batch has no device");
   if (!b->planned) return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - nothing to re-arm: the batch has not been planned (waa_render / waa_plan_describe)");
+  if (!b->prepass_note.empty())
+    return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - cannot re-arm: the plan holds param values rendered from the graph at plan time "
+                                       "(source playbackRate / detune or panner position / orientation driven from the graph), which new "
+                                       "audio may change: create a new batch");
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(hipStreamSynchronize(b->stream));  // (the previous render and its downloads are over before its inputs are overwritten)
   b->rearmed = true;

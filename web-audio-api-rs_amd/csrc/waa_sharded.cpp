@@ -192,7 +192,13 @@ waa_status waa_render_sharded(const waa_sharded_job* job, double* seconds) {
     std::lock_guard<std::mutex> l(trace_lock);
     fprintf(stderr, "[shard %u.%u] %8.2f ms  %s\n", sh.slot, sh.k, ms, what);
   };
-  // reuse_batches: downloaded sub-batches wait here, by (slot, contexts), for a later sub-batch of the same size (waa_batch_rearm)
+  // An AudioParam with an input from the graph: a source's playbackRate / detune or a panner's position / orientation among them
+  // is resolved by rendering the modulating subgraph at plan time, which may read the streamed source.  Such a plan is not
+  // planned ahead of its upload, and it is not re-armed for another sub-batch's audio (waa_batch_rearm refuses it).
+  bool modulated = false;
+  for (uint32_t e = 0; e < job->graph->n_edges; e++) modulated |= (job->graph->edges[e].to_input & 0x80000000u) != 0;
+  const bool reuse = job->reuse_batches && !modulated;
+  // reuse: downloaded sub-batches wait here, by (slot, contexts), for a later sub-batch of the same size (waa_batch_rearm)
   std::mutex pool_lock;
   std::map<std::pair<uint32_t, uint32_t>, std::vector<waa_batch*>> pool;
   auto run = [&](const Shard& sh) {
@@ -202,7 +208,7 @@ waa_status waa_render_sharded(const waa_sharded_job* job, double* seconds) {
     stamp(sh, "start");
     int st = WAA_OK;
     bool reused = false;
-    if (job->reuse_batches) {
+    if (reuse) {
       std::lock_guard<std::mutex> l(pool_lock);
       auto& v = pool[{sh.slot, sh.hi - sh.lo}];
       if (!v.empty()) {
@@ -227,8 +233,6 @@ waa_status waa_render_sharded(const waa_sharded_job* job, double* seconds) {
     // (Not when an AudioParam is modulated from the graph: that plan renders the modulating subgraph, which may read the source.)
     bool preplanned = false;
     if (!st && streamed) {
-      bool modulated = false;
-      for (uint32_t e = 0; e < job->graph->n_edges; e++) modulated |= (job->graph->edges[e].to_input & 0x80000000u) != 0;
       b->defer_fill = true;
       const char* src = static_cast<const char*>(job->host_in) + (size_t)sh.lo * row_in;
       st = job->in_pcm16 ? waa_source_set_buffer_pcm16_batch(b, job->source_node, reinterpret_cast<const int16_t*>(src), job->in_channels,
@@ -277,14 +281,14 @@ waa_status waa_render_sharded(const waa_sharded_job* job, double* seconds) {
         down[sh.slot].done();
       }
     }
-    if (b && job->reuse_batches && !st) {
+    if (b && reuse && !st) {
       std::lock_guard<std::mutex> l(pool_lock);
       pool[{sh.slot, sh.hi - sh.lo}].push_back(b);
       b = nullptr;
     }
     if (b) waa_batch_destroy(b);
     window[sh.slot].leave();
-    stamp(sh, job->reuse_batches && !st ? "kept for re-use" : "destroyed");
+    stamp(sh, reuse && !st ? "kept for re-use" : "destroyed");
   };
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<std::thread> threads;

@@ -112,7 +112,9 @@ def render_sharded(build: Callable, host_in, host_out, devices: Sequence[int] = 
     host_out: [N, n_out, length] float32 (out_pcm16=True: [N, length, n_out] int16), filled with every context's AudioBuffer.
     pull(ctx, lo, hi): optional control-side work per sub-batch after its render (e.g. the batched analyser pull).
     reuse: build() configures every sub-batch identically (waa_sharded_job.reuse_batches): a downloaded sub-batch is re-armed for a
-        later one of the same size instead of being destroyed — no second creation, setup or plan.
+        later one of the same size instead of being destroyed — no second creation, setup or plan.  Ignored when the graph has
+        an edge into an AudioParam: such a plan may hold values rendered from a sub-batch's own audio (a source's playbackRate
+        driven by the streamed source), so every sub-batch is created and planned anew.
     Returns {"seconds": wall time, "shards": [(device, lo, hi), ...]}.  Raises the first sub-batch error."""
     from .api import SHARD_FN, ShardedJob, WaaError
     devices = [int(d) for d in devices]
