@@ -87,7 +87,8 @@ enum {
   WAA_NODE_IIR_FILTER = 10,     /* src/node/iir_filter.rs:323-405 */
   WAA_NODE_DELAY = 11,          /* src/node/delay.rs:428-745 incl. the cycle breaker of graph.rs:323-487 */
   WAA_NODE_OSCILLATOR = 12,     /* src/node/oscillator.rs:323-660 (on-device source) */
-  WAA_NODE_KIND_COUNT = 13
+  WAA_NODE_DYNAMICS_COMPRESSOR = 13, /* src/node/dynamics_compressor.rs:330-479 (level -> serial detector -> look-ahead gain) */
+  WAA_NODE_KIND_COUNT = 14
 };
 
 /* src/node/audio_node.rs ChannelCountMode / ChannelInterpretation */
@@ -113,6 +114,14 @@ enum { WAA_PARAM_STEREO_PANNER_PAN = 0 };
 enum { WAA_PARAM_CONSTANT_OFFSET = 0 };
 enum { WAA_PARAM_DELAY_DELAY_TIME = 0 };
 enum { WAA_PARAM_OSCILLATOR_FREQUENCY = 0, WAA_PARAM_OSCILLATOR_DETUNE = 1 };
+/* DynamicsCompressorNode (dynamics_compressor.rs:187-247): all five are k-rate with a fixed automation rate */
+enum {
+  WAA_PARAM_COMPRESSOR_THRESHOLD = 0,
+  WAA_PARAM_COMPRESSOR_KNEE = 1,
+  WAA_PARAM_COMPRESSOR_RATIO = 2,
+  WAA_PARAM_COMPRESSOR_ATTACK = 3,
+  WAA_PARAM_COMPRESSOR_RELEASE = 4
+};
 /* src/node/oscillator.rs OscillatorType */
 enum { WAA_OSC_SINE = 0, WAA_OSC_SQUARE = 1, WAA_OSC_SAWTOOTH = 2, WAA_OSC_TRIANGLE = 3, WAA_OSC_CUSTOM = 4 };
 enum {

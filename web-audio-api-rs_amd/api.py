@@ -40,6 +40,7 @@ NODE_STEREO_PANNER, NODE_PANNER, NODE_ANALYSER, NODE_WAVESHAPER, NODE_CONSTANT_S
 NODE_IIR_FILTER = 10
 NODE_DELAY = 11
 NODE_OSCILLATOR = 12
+NODE_DYNAMICS_COMPRESSOR = 13
 OSCILLATOR_TYPE = {"sine": 0, "square": 1, "sawtooth": 2, "triangle": 3, "custom": 4}
 MAX_IIR_COEFFS = 20
 PARAM_INPUT = 0x80000000  # WAA_PARAM_INPUT(param): edge into an AudioParam of the target node
@@ -772,6 +773,44 @@ class StereoPannerNode(AudioNode):
         self.params = [self.pan]
 
 
+class DynamicsCompressorNode(AudioNode):
+    """src/node/dynamics_compressor.rs — the five k-rate AudioParams and the channel-config constraints; the node itself is
+    rendered by the library (waa_compressor.hip), nothing is computed here."""
+    kind = NODE_DYNAMICS_COMPRESSOR
+    default_channel_config = (2, "clamped-max", "speakers")
+
+    def __init__(self, ctx, attack: float = 0.003, knee: float = 30.0, ratio: float = 12.0, release: float = 0.25,
+                 threshold: float = -24.0, **kw):
+        # DynamicsCompressorNode::new asserts both before anything else (dynamics_compressor.rs:184-185)
+        self._assert_valid_channel_count(kw.get("channel_count") or 2)
+        self._assert_valid_channel_count_mode(kw.get("channel_count_mode") or "clamped-max")
+        super().__init__(ctx, **kw)
+        self.threshold = AudioParam(self, 0, threshold)
+        self.knee = AudioParam(self, 1, knee)
+        self.ratio = AudioParam(self, 2, ratio)
+        self.attack = AudioParam(self, 3, attack)
+        self.release = AudioParam(self, 4, release)
+        self.params = [self.threshold, self.knee, self.ratio, self.attack, self.release]
+
+    @staticmethod
+    def _assert_valid_channel_count(count: int):  # dynamics_compressor.rs:72-79
+        if int(count) > 2:
+            raise WaaError(2, "NotSupportedError - DynamicsCompressorNode channel count cannot be greater than two")
+
+    @staticmethod
+    def _assert_valid_channel_count_mode(mode: str):  # dynamics_compressor.rs:88-96
+        if mode == "max":
+            raise WaaError(2, "NotSupportedError - DynamicsCompressorNode channel count mode cannot be set to max")
+
+    def set_channel_count(self, v: int):
+        self._assert_valid_channel_count(v)
+        super().set_channel_count(v)
+
+    def set_channel_count_mode(self, v: str):
+        self._assert_valid_channel_count_mode(v)
+        super().set_channel_count_mode(v)
+
+
 class AudioListener:
     """src/spatial.rs:127-144 — shared by every PannerNode of the context."""
 
@@ -1151,6 +1190,9 @@ class OfflineAudioContext:
 
     def create_periodic_wave(self, **kw):
         return PeriodicWave(self, **kw)
+
+    def create_dynamics_compressor(self, **kw):
+        return DynamicsCompressorNode(self, **kw)
 
     def create_delay(self, max_delay_time: float = 1.0, **kw):
         return DelayNode(self, max_delay_time=max_delay_time, **kw)

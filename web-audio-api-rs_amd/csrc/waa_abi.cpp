@@ -151,6 +151,19 @@ waa_status waa_batch_create(const waa_graph_desc* g, uint32_t n_inst, uint32_t n
         if (n.mode == WAA_COUNT_MODE_MAX)
           return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - ConvolverNode channel count mode cannot be set to max");
         break;
+      case WAA_NODE_DYNAMICS_COMPRESSOR: {  // dynamics_compressor.rs:182-247 (and :72-96 for the two constraints)
+        if (n.cc > 2)
+          return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - DynamicsCompressorNode channel count cannot be greater than two");
+        if (n.mode == WAA_COUNT_MODE_MAX)
+          return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - DynamicsCompressorNode channel count mode cannot be set to max");
+        P(WAA_PARAM_COMPRESSOR_THRESHOLD).init(n_inst, -24.f, -100.f, 0.f);
+        P(WAA_PARAM_COMPRESSOR_KNEE).init(n_inst, 30.f, 0.f, 40.f);
+        P(WAA_PARAM_COMPRESSOR_RATIO).init(n_inst, 12.f, 1.f, 20.f);
+        P(WAA_PARAM_COMPRESSOR_ATTACK).init(n_inst, 0.003f, 0.f, 1.f);
+        P(WAA_PARAM_COMPRESSOR_RELEASE).init(n_inst, 0.25f, 0.f, 1.f);
+        for (auto& ps : n.params) ps.k_rate = true;
+        break;
+      }
       case WAA_NODE_ANALYSER: {
         int fs = n.desc.i[0] ? n.desc.i[0] : 2048;
         if (fs < 32 || fs > 32768 || (fs & (fs - 1)))
@@ -1441,6 +1454,11 @@ static int run_steps(waa_batch* b) {
       case 16: e = timed(st.profile_slot, [&] { launch_qgemm(st.qgemm, b->stream); }); break;
       case 17: e = timed(st.profile_slot, [&] { launch_hrtf(st.hrtf, b->stream); }); break;
       case 20: e = timed(st.profile_slot, [&] { launch_osfft(st.osfft, b->stream); }); break;
+      case 21:  // (never inside a feedback loop: always the whole render)
+        if ((e = timed(st.slot_fwd, [&] { launch_compressor_level(st.comp, b->stream); }))) break;
+        if ((e = timed(st.slot_mac, [&] { launch_compressor_detector(st.comp, b->stream); }))) break;
+        e = timed(st.slot_inv, [&] { launch_compressor_apply(st.comp, b->stream); });
+        break;
       case 12:
         if (st.hp.coefs) e = timed(st.profile_slot, [&] { launch_biquad_hp(st.hp, b->stream); });
         break;

@@ -224,7 +224,7 @@ struct ProfileEntry {
 };
 
 struct Step {
-  int kind = 0;  // 15 link table of a frozen-state node, 16 one resampling stage of an oversampled WaveShaper (qgemm_kernel), 17 HRTF FIR; 0 chain (interpreter kernel), 1 streaming biquad kernel, 2 FFT convolver, 3 zero-fill, 4 direct FIR, 5 per-frame biquad coefficients, 6 streaming IIR kernel, 7 delay gather, 8 feedback loop, 9 oscillator, 10 dynamic-count group (dyn_kernel), 11 convolver codes, 12 digest of a shared per-frame coefficient table, 13 per-frame panner geometry, 14 automation timelines replayed on the device
+  int kind = 0;  // 21 DynamicsCompressorNode (level, detector, apply: waa_compressor.hip), 15 link table of a frozen-state node, 16 one resampling stage of an oversampled WaveShaper (qgemm_kernel), 17 HRTF FIR; 0 chain (interpreter kernel), 1 streaming biquad kernel, 2 FFT convolver, 3 zero-fill, 4 direct FIR, 5 per-frame biquad coefficients, 6 streaming IIR kernel, 7 delay gather, 8 feedback loop, 9 oscillator, 10 dynamic-count group (dyn_kernel), 11 convolver codes, 12 digest of a shared per-frame coefficient table, 13 per-frame panner geometry, 14 automation timelines replayed on the device
   ChainDesc chain{};
   BiquadStreamDesc bq{};
   BiquadScanCtl scan{};   // kind 1 with scan.payload: the time-parallel form (waa_biquad_scan.hip)
@@ -244,6 +244,7 @@ struct Step {
   QGemmDesc qgemm{};
   OsFftDesc osfft{};      // kind 20: the oversampled WaveShaper in one launch (waa_osfft.hip)
   HrtfDesc hrtf{};
+  CompDesc comp{};        // kind 21 (profile slots: slot_fwd = level, slot_mac = detector, slot_inv = apply)
   int slot_fwd = -1, slot_mac = -1, slot_inv = -1;
   void* zero_ptr = nullptr;
   size_t zero_bytes = 0;
@@ -482,6 +483,11 @@ inline bool is_frozen_node(const Node& n) {
   return (n.desc.kind == WAA_NODE_WAVESHAPER && n.has_curve && n.desc.i[0] != WAA_OVERSAMPLE_NONE) ||
          (n.desc.kind == WAA_NODE_PANNER && n.desc.i[0] == WAA_PANNING_HRTF);
 }
+
+// DynamicsCompressorNode: rendered node-major by launches of its own (waa_compressor.hip), input and output materialised
+inline bool is_compressor(const Node& n) { return n.desc.kind == WAA_NODE_DYNAMICS_COMPRESSOR; }
+// quanta of look-ahead, in f32 exactly as dynamics_compressor.rs:253-254 sizes its ring (ring - 1)
+inline uint32_t compressor_delay_quanta(float sample_rate) { return (uint32_t)std::ceil(sample_rate * 0.006f / (float)RQ); }
 
 inline int check_node(waa_batch* b, uint32_t node, uint32_t kind) {
   if (!b) return fail(WAA_ERR_INVALID_ARGUMENT, "null batch");

@@ -243,6 +243,30 @@ struct IirStreamDesc {
 int iir_padded_states(int n_states);  // kernel state count for a filter with n_states state variables
 void launch_iir_stream(const IirStreamDesc& d, void* stream);
 
+// ---- DynamicsCompressorNode (dynamics_compressor.rs:330-479), node-major in three launches (waa_compressor.hip) ----------
+// The block constants of dynamics_compressor.rs:353-389 for one render quantum, computed on the host in f32 with the libm calls
+// the reference makes (waa_plan_comp.cpp::plan_compressor).  Three 16-byte groups: gain computer, make-up, detector.
+struct CompRow {
+  float thr, lo, hi, half_knee;        // shifted threshold, thr - half_knee, thr + half_knee, knee / 2
+  float knee_partial, ratio, makeup, pad;
+  float a_tau, a_one, r_tau, r_one;    // attack_tau, 1 - attack_tau, release_tau, 1 - release_tau
+};
+struct CompDesc {
+  SignalRef in;            // the node's mixed input, 1 or 2 channels
+  uint64_t in_valid;       // frames of `in` that may be read (zeros beyond: a source read in place)
+  SignalRef out;           // same channel count
+  float* xl;               // [n_inst][frames]: attenuation xL in dB (level), overwritten in place by the detector's yL
+  const CompRow* rows;     // row of (inst, quantum) = rows[inst * row_inst_stride + quantum * row_q_stride]
+  uint32_t row_inst_stride, row_q_stride;  // 0: shared by every instance / one row for the whole render
+  uint32_t n_inst, n_quanta;
+  uint64_t frames;         // padded frames per channel (a multiple of TILE)
+  uint32_t delay_frames;   // 128 * D: the look-ahead ring of dynamics_compressor.rs:253-254, 452-461
+  int32_t nch;
+};
+void launch_compressor_level(const CompDesc& d, void* stream);
+void launch_compressor_detector(const CompDesc& d, void* stream);
+void launch_compressor_apply(const CompDesc& d, void* stream);
+
 // ---- ConvolverNode (convolver.rs:343-490 + fft-convolver), node-major overlap-save ------------
 // out[co] = sum over terms t with t.out_ch == co of  IR[t.ir_ch] * in[t.in_ch]   (linear convolution)
 struct ConvTerm {

@@ -1211,6 +1211,9 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
         return fail(WAA_ERR_OUT_OF_SCOPE,
                     "position / orientation of panner node %u are modulated from the graph: resolved at plan time on the device for a "
                     "single-valued AudioListener only (audio-rate listener automation next to it, or a plan-only batch)", ed.to);
+      if (k == WAA_NODE_DYNAMICS_COMPRESSOR)
+        return fail(WAA_ERR_OUT_OF_SCOPE, "DynamicsCompressorNode %u: an edge into its AudioParam %u — the block constants of the node are computed on the host from "
+                                          "host-known k-rate values (dynamics_compressor.rs:353-389): a param driven from the graph is out of scope", ed.to, pid);
       if (!(k == WAA_NODE_GAIN || k == WAA_NODE_BIQUAD || k == WAA_NODE_DELAY || k == WAA_NODE_STEREO_PANNER ||
             k == WAA_NODE_CONSTANT_SOURCE || k == WAA_NODE_OSCILLATOR || source_rate || panner_geom))
         return fail(WAA_ERR_OUT_OF_SCOPE, "audio-rate modulation of a host-evaluated param (node %u) is out of scope", ed.to);
@@ -1247,6 +1250,10 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
         for (int e : pe) stack.push_back(b->edges[e].from);
     }
   }
+  for (uint32_t i = 0; i < N; i++)
+    if (b->nodes[i].live && is_compressor(b->nodes[i]) && scc_of[i] >= 0)
+      return fail(WAA_ERR_OUT_OF_SCOPE, "DynamicsCompressorNode %u inside a feedback loop is out of scope: its detector is rendered over the whole render "
+                                        "by one launch, not quantum by quantum", i);
   // (prepass) a modulated source that itself feeds the modulating subgraph of a modulated source: its own schedule is
   // not known before ITS modulation has been resolved — a second prepass level nobody has asked for yet; refused loudly
   // (it used to be skipped by plan_single and the outer param chain read an empty signal)
@@ -1501,6 +1508,12 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
               const bool in_loop = id < b->cut.size() && b->cut[id];
               const int64_t qc = in_loop ? (int64_t)q - 1 : (int64_t)q;
               c = qc >= 0 ? in_cnt[id][qc] : 1;
+            } else if (kind == WAA_NODE_DYNAMICS_COMPRESSOR) {
+              // the output is the quantum that entered the look-ahead ring D quanta ago, with its channel count; the ring
+              // starts out silent (dynamics_compressor.rs:343-349, 452-468)
+              const int64_t qs = (int64_t)q - (int64_t)compressor_delay_quanta(b->sr);
+              a = qs >= 0 ? in_act[id][qs] : 0;
+              c = qs >= 0 ? in_cnt[id][qs] : 1;
             } else if (kind == WAA_NODE_GAIN && !zero_gain[id].empty() && zero_gain[id][q]) {
               a = 0;
             } else if (kind == WAA_NODE_WAVESHAPER && n.has_curve && !a) {
@@ -1690,7 +1703,7 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
       const Node& c = b->nodes[e.to];
       const uint32_t ck = c.desc.kind;
       const bool other_loop = scc_of[e.to] >= 0 && !(scc_of[e.to] == scc_of[id] && block_loop(id));
-      if ((e.to_input & 0x80000000u) || other_loop || (ck == WAA_NODE_CONVOLVER && c.has_ir) || is_frozen_node(c) || c.in_nch > 2 ||
+      if ((e.to_input & 0x80000000u) || other_loop || (ck == WAA_NODE_CONVOLVER && c.has_ir) || is_frozen_node(c) || is_compressor(c) || c.in_nch > 2 ||
           n.out_nch > 2)
         ok = false;
     }
@@ -1710,6 +1723,7 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
     const uint32_t kind = n.desc.kind;
     if (kind == WAA_NODE_DESTINATION || kind == WAA_NODE_ANALYSER || kind == WAA_NODE_CONVOLVER || kind == WAA_NODE_DELAY) mat = true;
     if (is_frozen_node(n)) mat = true;  // rendered node-major (waa_frozen.hip)
+    if (is_compressor(n)) mat = true;   // rendered node-major (waa_compressor.hip)
     // (a GainNode of a block-scheduled loop may ride on an input edge of its consumer, see above)
     const bool relaxed = kind == WAA_NODE_GAIN && block_loop(id);
     if (scc_of[id] >= 0 && !relaxed) mat = true;  // loop members publish their own signal
@@ -1719,7 +1733,7 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
       if (e.from == id && b->nodes[e.to].live) {
         live_consumers++;
         const Node& c = b->nodes[e.to];
-        if ((c.desc.kind == WAA_NODE_CONVOLVER && c.has_ir) || is_frozen_node(c)) mat = true;
+        if ((c.desc.kind == WAA_NODE_CONVOLVER && c.has_ir) || is_frozen_node(c) || is_compressor(c)) mat = true;
         if (c.desc.kind == WAA_NODE_DELAY) {
           // a DelayNode mixes its inputs like a summing chain head (node_input_signal): materialised unless foldable
           if (relaxed)
@@ -1790,12 +1804,12 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
       const Node& c = b->nodes[e.to];
       const uint32_t ck = c.desc.kind;
       if ((e.to_input & 0x80000000u) || (scc_of[e.to] >= 0 && !block_loop(e.to)) || (ck == WAA_NODE_CONVOLVER && c.has_ir) ||
-          is_frozen_node(c) || ck == WAA_NODE_IIR_FILTER)
+          is_frozen_node(c) || is_compressor(c) || ck == WAA_NODE_IIR_FILTER)
         shared_ok = false;
     }
     if (!shared_ok && (n_live != 1 || consumer < 0)) continue;
     const Node& c = b->nodes[(uint32_t)(shared_ok ? 0 : consumer)];
-    const bool conv = !shared_ok && c.desc.kind == WAA_NODE_CONVOLVER && c.has_ir;
+    const bool conv = !shared_ok && ((c.desc.kind == WAA_NODE_CONVOLVER && c.has_ir) || is_compressor(c));  // (both take a bounded view)
     bool frozen_ok = shared_ok;
     if (!shared_ok && is_frozen_node(c) && frozen_src[(uint32_t)consumer] == (int)id) {
       if (c.desc.kind == WAA_NODE_PANNER) {
@@ -1979,6 +1993,11 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
       if (e) return e;
       return plan_oscillator(b, id);
     }
+    if (is_compressor(term)) {
+      int e = alloc_signal(term);
+      if (e) return e;
+      return plan_compressor(b, id);
+    }
     if (is_frozen_node(term)) {
       if (scc_of[id] >= 0)
         return fail(WAA_ERR_OUT_OF_SCOPE, "an oversampled WaveShaperNode / HRTF PannerNode inside a feedback loop is out of scope (node %u)", id);
@@ -2144,6 +2163,10 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
   if (b->prepass && (count_change_found || b->force_dynamic))
     return fail(WAA_ERR_OUT_OF_SCOPE, "the graph that modulates a source's playbackRate / detune needs exact per-quantum channel counts: out of scope");
   if (count_change_found || b->force_dynamic) {
+    for (uint32_t i = 0; i < N; i++)
+      if (b->nodes[i].live && is_compressor(b->nodes[i]))
+        return fail(WAA_ERR_OUT_OF_SCOPE, "DynamicsCompressorNode %u in a graph that needs exact per-quantum channel counts (dyn_kernel) is out of scope: "
+                                          "the node is rendered by static plans only", i);
     DynPlanCtx dc{items, units, scc_of, alloc_signal, plan_single, count_change_found, mixed_buffer_counts};
     return plan_dynamic_groups(b, dc);
   }

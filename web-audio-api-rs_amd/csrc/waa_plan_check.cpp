@@ -52,6 +52,10 @@ StepIo step_io(const Step& st) {
       io.reads.push_back(st.conv.in.base);
       io.writes.push_back(st.conv.out.base);
       break;
+    case 21:
+      io.reads.push_back(st.comp.in.base);
+      io.writes.push_back(st.comp.out.base);
+      break;
     case 3:
       io.writes.push_back(st.zero_ptr);
       break;

@@ -399,6 +399,7 @@ void default_channel_config(Node& n, uint32_t n_out) {
     case WAA_NODE_CONVOLVER:
     case WAA_NODE_STEREO_PANNER:
     case WAA_NODE_PANNER:
+    case WAA_NODE_DYNAMICS_COMPRESSOR:
       mode = WAA_COUNT_MODE_CLAMPED_MAX;
       break;
     default: break;

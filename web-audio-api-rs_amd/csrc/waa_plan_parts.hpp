@@ -79,6 +79,7 @@ int conv_block_size(const waa_batch* b, const Node& n);
 // dies out inside the partitions the response occupies anyway (true: folded; the Biquad then costs nothing per render)
 bool conv_fold_biquad_into_ir(const waa_batch* b, Node& conv, const Node& q);
 int plan_convolver(waa_batch* b, uint32_t id);
+int plan_compressor(waa_batch* b, uint32_t id);
 int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector<OpDesc>& ops, int* out_nch);
 void default_channel_config(Node& n, uint32_t n_out);
 
