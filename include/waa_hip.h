@@ -88,8 +88,12 @@ enum {
   WAA_NODE_DELAY = 11,          /* src/node/delay.rs:428-745 incl. the cycle breaker of graph.rs:323-487 */
   WAA_NODE_OSCILLATOR = 12,     /* src/node/oscillator.rs:323-660 (on-device source) */
   WAA_NODE_DYNAMICS_COMPRESSOR = 13, /* src/node/dynamics_compressor.rs:330-479 (level -> serial detector -> look-ahead gain) */
-  WAA_NODE_KIND_COUNT = 14
+  WAA_NODE_CHANNEL_SPLITTER = 14, /* src/node/channel_splitter.rs:183-210 (one input, i[0] mono outputs: output k = channel k of the input) */
+  WAA_NODE_CHANNEL_MERGER = 15,   /* src/node/channel_merger.rs:145-172 (i[0] mono inputs, one output: channel k = input k) */
+  WAA_NODE_KIND_COUNT = 16
 };
+/* ChannelSplitterOptions::default / ChannelMergerOptions::default (channel_splitter.rs:90-101, channel_merger.rs:72-83) */
+#define WAA_DEFAULT_NUMBER_OF_PORTS 6
 
 /* src/node/audio_node.rs ChannelCountMode / ChannelInterpretation */
 enum { WAA_COUNT_MODE_MAX = 0, WAA_COUNT_MODE_CLAMPED_MAX = 1, WAA_COUNT_MODE_EXPLICIT = 2 };
@@ -147,6 +151,14 @@ enum {
  *     CONVOLVER   i[0] = disable_normalization (0/1)
  *     OSCILLATOR  i[0] = type (WAA_OSC_*; CUSTOM needs waa_oscillator_set_periodic_wave); scheduled with
  *                 waa_source_start / waa_source_stop like the other AudioScheduledSourceNodes
+ *     CHANNEL_SPLITTER  i[0] = number_of_outputs (0 = the default, 6; [1, 32]: IndexSizeError, channel_splitter.rs:23-30).
+ *                 channel_count must equal number_of_outputs, the mode must be explicit, the interpretation discrete
+ *                 (InvalidStateError, channel_splitter.rs:39-78, 146-161); the effective count is number_of_outputs.
+ *     CHANNEL_MERGER    i[0] = number_of_inputs (0 = the default, 6; [1, 32]: IndexSizeError, channel_merger.rs:21-28).
+ *                 channel_count must be 1 and the mode explicit (InvalidStateError, channel_merger.rs:37-60, 122-127);
+ *                 the interpretation is free (default: speakers).
+ *                 Both kinds are rendered by static plans only: WAA_ERR_OUT_OF_SCOPE inside a feedback loop and in a
+ *                 graph that needs exact per-quantum channel counts.
  *     DELAY       d[0] = max_delay_time in seconds (0 = the default, 1 s); must be > 0 and < 180
  *                 (NotSupportedError, delay.rs:290-293).  Graph cycles through a DelayNode are rendered (the delay
  *                 is clamped to one render quantum inside a loop, delay.rs:693-701); cycles without one are muted.
@@ -161,6 +173,10 @@ typedef struct {
 } waa_node_desc;
 
 /* AudioNode::connect_from_output_to_input(from, output, to, input); mirrors graph.rs Edge.
+ * from_output must be below the producer's number of outputs (i[0] of a ChannelSplitterNode, 1 for every other kind) and
+ * a to_input that is not a param below the consumer's number of inputs (i[0] of a ChannelMergerNode, 1 otherwise):
+ * "IndexSizeError - output port {} is out of bounds" / "IndexSizeError - input port {} is out of bounds"
+ * (src/node/audio_node.rs:270-279), at waa_batch_create, waa_connect and waa_disconnect alike.
  * `node.connect(&audio_param)` (audio-rate modulation, src/param.rs:686-795: the param is a graph node with
  * channel count 1 / explicit / discrete whose summed input is added to the intrinsic value) is expressed as an
  * edge into the OWNING node with to_input = WAA_PARAM_INPUT(param id).  Supported on the device for a-rate

@@ -41,6 +41,9 @@ NODE_IIR_FILTER = 10
 NODE_DELAY = 11
 NODE_OSCILLATOR = 12
 NODE_DYNAMICS_COMPRESSOR = 13
+NODE_CHANNEL_SPLITTER = 14
+NODE_CHANNEL_MERGER = 15
+MAX_CHANNELS = 32  # src/lib.rs:21
 OSCILLATOR_TYPE = {"sine": 0, "square": 1, "sawtooth": 2, "triangle": 3, "custom": 4}
 MAX_IIR_COEFFS = 20
 PARAM_INPUT = 0x80000000  # WAA_PARAM_INPUT(param): edge into an AudioParam of the target node
@@ -363,6 +366,10 @@ class AudioParam:
 class AudioNode:
     kind = -1
     default_channel_config = (2, "max", "speakers")
+    # AudioNode::number_of_inputs / number_of_outputs as far as connect() looks at them: one port each, except the
+    # ChannelSplitterNode's outputs and the ChannelMergerNode's inputs
+    number_of_inputs = 1
+    number_of_outputs = 1
 
     def __init__(self, ctx: "OfflineAudioContext", channel_count=None, channel_count_mode=None,
                  channel_interpretation=None):
@@ -395,10 +402,16 @@ class AudioNode:
         if isinstance(dest, AudioParam):
             if dest._node.context is not self.context:
                 raise WaaError(1, "InvalidAccessError - Attempting to connect nodes from different contexts")
+            if not 0 <= output < self.number_of_outputs:  # param.rs connect: the same assertion on the output port
+                raise WaaError(1, f"IndexSizeError - output port {output} is out of bounds")
             self.context._connect((self.id, output, dest._node.id, PARAM_INPUT | dest._pid))
             return dest
         if dest.context is not self.context:
             raise WaaError(1, "InvalidAccessError - Attempting to connect nodes from different contexts")
+        if not 0 <= output < self.number_of_outputs:  # audio_node.rs:270-279
+            raise WaaError(1, f"IndexSizeError - output port {output} is out of bounds")
+        if not 0 <= input < dest.number_of_inputs:
+            raise WaaError(1, f"IndexSizeError - input port {input} is out of bounds")
         self.context._connect((self.id, output, dest.id, input))
         return dest
 
@@ -408,7 +421,7 @@ class AudioNode:
             dctx = dest._node.context if isinstance(dest, AudioParam) else dest.context
             if dctx is not self.context:
                 raise WaaError(1, "InvalidAccessError - Attempting to disconnect nodes from different contexts")
-        if output is not None and output != 0:
+        if output is not None and not 0 <= output < self.number_of_outputs:
             raise WaaError(1, f"IndexSizeError - output port {output} is out of bounds")
         to = None if dest is None else (dest._node.id if isinstance(dest, AudioParam) else dest.id)
         ti = None if dest is None else (PARAM_INPUT | dest._pid if isinstance(dest, AudioParam) else input)
@@ -424,7 +437,8 @@ class AudioNode:
         self.disconnect(dest, output)
 
     def disconnect_dest_from_output_to_input(self, dest, output: int, input: int):
-        if input != 0:
+        n_in = 1 if isinstance(dest, AudioParam) else dest.number_of_inputs
+        if not 0 <= input < n_in:
             raise WaaError(1, f"IndexSizeError - input port {input} is out of bounds")
         self.disconnect(dest, output, input)
 
@@ -1034,6 +1048,102 @@ class DelayNode(AudioNode):
         d.d[0] = self.max_delay_time
 
 
+def _assert_valid_number_of_ports(n: int):
+    # assert_valid_number_of_channels, channel_splitter.rs:23-30 / channel_merger.rs:21-28
+    if not 0 < n <= MAX_CHANNELS:
+        raise WaaError(1, f"IndexSizeError - Invalid number of channels: {n} is outside range [1, {MAX_CHANNELS}]")
+
+
+class ChannelSplitterNode(AudioNode):
+    """src/node/channel_splitter.rs:80-210 (ChannelSplitterOptions{number_of_outputs = 6}; count = number_of_outputs,
+    explicit, discrete — all three fixed).  One input, `number_of_outputs` mono outputs: output k carries channel k of the
+    input, silence where the input has no such channel.  Connect an output with `connect(dest, output=k)`."""
+
+    kind = NODE_CHANNEL_SPLITTER
+    DEFAULT_NUMBER_OF_OUTPUTS = 6
+
+    def __init__(self, ctx, number_of_outputs: int = 6, channel_count=None, channel_count_mode=None, channel_interpretation=None):
+        number_of_outputs = int(number_of_outputs)
+        _assert_valid_number_of_ports(number_of_outputs)
+        # (ChannelSplitterNode::new, :146-161: a count other than the default of 6 must equal number_of_outputs)
+        if channel_count is not None and channel_count != self.DEFAULT_NUMBER_OF_OUTPUTS:
+            self._assert_count(channel_count, number_of_outputs)
+        if channel_count_mode is not None:
+            self._assert_mode(channel_count_mode)
+        if channel_interpretation is not None:
+            self._assert_interpretation(channel_interpretation)
+        self.number_of_outputs = number_of_outputs
+        self.default_channel_config = (number_of_outputs, "explicit", "discrete")
+        super().__init__(ctx)
+
+    @staticmethod
+    def _assert_count(count, number_of_outputs):
+        if count != number_of_outputs:
+            raise WaaError(3, "InvalidStateError - channel count of ChannelSplitterNode must be equal to number of outputs")
+
+    @staticmethod
+    def _assert_mode(mode):
+        if mode != "explicit":
+            raise WaaError(3, "InvalidStateError - channel count of ChannelSplitterNode must be set to Explicit")
+
+    @staticmethod
+    def _assert_interpretation(interpretation):
+        if interpretation != "discrete":
+            raise WaaError(3, "InvalidStateError - channel interpretation of ChannelSplitterNode must be set to Discrete")
+
+    # channel_splitter.rs:120-134: the setters only assert (the values cannot change)
+    def set_channel_count(self, v: int):
+        self._assert_count(int(v), self.number_of_outputs)
+
+    def set_channel_count_mode(self, v: str):
+        self._assert_mode(v)
+
+    def set_channel_interpretation(self, v: str):
+        self._assert_interpretation(v)
+
+    def _fill_desc(self, d):
+        d.i[0] = self.number_of_outputs
+
+
+class ChannelMergerNode(AudioNode):
+    """src/node/channel_merger.rs:62-172 (ChannelMergerOptions{number_of_inputs = 6}; count 1 and explicit are fixed, the
+    interpretation is free: speakers).  `number_of_inputs` inputs, each mixed to mono; one output with `number_of_inputs`
+    channels, channel k = input k.  Connect to an input with `connect(merger, input=k)`."""
+
+    kind = NODE_CHANNEL_MERGER
+    default_channel_config = (1, "explicit", "speakers")
+
+    def __init__(self, ctx, number_of_inputs: int = 6, channel_count=None, channel_count_mode=None, channel_interpretation=None):
+        number_of_inputs = int(number_of_inputs)
+        _assert_valid_number_of_ports(number_of_inputs)
+        if channel_count is not None:
+            self._assert_count(channel_count)
+        if channel_count_mode is not None:
+            self._assert_mode(channel_count_mode)
+        self.number_of_inputs = number_of_inputs
+        super().__init__(ctx, channel_interpretation=channel_interpretation)
+
+    @staticmethod
+    def _assert_count(count):
+        if count != 1:
+            raise WaaError(3, "InvalidStateError - channel count of ChannelMergerNode must be equal to 1")
+
+    @staticmethod
+    def _assert_mode(mode):
+        if mode != "explicit":
+            raise WaaError(3, "InvalidStateError - channel count of ChannelMergerNode must be set to Explicit")
+
+    # channel_merger.rs:102-110
+    def set_channel_count(self, v: int):
+        self._assert_count(int(v))
+
+    def set_channel_count_mode(self, v: str):
+        self._assert_mode(v)
+
+    def _fill_desc(self, d):
+        d.i[0] = self.number_of_inputs
+
+
 class RenderedBatch:
     """What start_rendering_sync returns: one AudioBuffer per instance (array [inst, ch, frames])."""
 
@@ -1193,6 +1303,12 @@ class OfflineAudioContext:
 
     def create_dynamics_compressor(self, **kw):
         return DynamicsCompressorNode(self, **kw)
+
+    def create_channel_splitter(self, number_of_outputs: int = 6, **kw):
+        return ChannelSplitterNode(self, number_of_outputs, **kw)
+
+    def create_channel_merger(self, number_of_inputs: int = 6, **kw):
+        return ChannelMergerNode(self, number_of_inputs, **kw)
 
     def create_delay(self, max_delay_time: float = 1.0, **kw):
         return DelayNode(self, max_delay_time=max_delay_time, **kw)

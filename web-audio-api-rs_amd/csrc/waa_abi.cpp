@@ -37,6 +37,17 @@ int32_t waa_device_count(void) {
   return n;
 }
 
+// number_of_outputs / number_of_inputs of a node (audio_node.rs; channel_splitter.rs:136-142, channel_merger.rs:112-118)
+static uint32_t node_outputs(const Node& n) { return n.desc.kind == WAA_NODE_CHANNEL_SPLITTER ? (uint32_t)n.desc.i[0] : 1u; }
+static uint32_t node_inputs(const Node& n) { return n.desc.kind == WAA_NODE_CHANNEL_MERGER ? (uint32_t)n.desc.i[0] : 1u; }
+static int check_ports(const waa_batch* b, uint32_t from, uint32_t from_output, uint32_t to, uint32_t to_input) {
+  if (from_output >= node_outputs(b->nodes[from]))
+    return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - output port %u is out of bounds", from_output);
+  if (!(to_input & 0x80000000u) && to_input >= node_inputs(b->nodes[to]))
+    return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - input port %u is out of bounds", to_input);
+  return 0;
+}
+
 waa_status waa_batch_create(const waa_graph_desc* g, uint32_t n_inst, uint32_t n_out, uint64_t length, float sr,
                             int32_t device, waa_batch** out) {
   if (!g || !out || g->n_nodes == 0 || n_inst == 0) return fail(WAA_ERR_INVALID_ARGUMENT, "invalid arguments");
@@ -58,9 +69,7 @@ waa_status waa_batch_create(const waa_graph_desc* g, uint32_t n_inst, uint32_t n
   b->lp = (uint64_t)b->n_tiles * TILE;
   for (uint32_t e = 0; e < g->n_edges; e++) {
     const waa_edge_desc& ed = g->edges[e];
-    if (ed.from >= g->n_nodes || ed.to >= g->n_nodes || ed.from_output != 0 ||
-        (ed.to_input != 0 && !(ed.to_input & 0x80000000u)))
-      return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - invalid edge %u", e);
+    if (ed.from >= g->n_nodes || ed.to >= g->n_nodes) return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - invalid edge %u", e);
     b->edges.push_back(ed);
   }
   b->edge_on.assign(b->edges.size(), 0u);
@@ -179,9 +188,39 @@ waa_status waa_batch_create(const waa_graph_desc* g, uint32_t n_inst, uint32_t n
         if (!(n.desc.d[1] < n.desc.d[2])) return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - Invalid min decibels");
         break;
       }
+      case WAA_NODE_CHANNEL_SPLITTER: {  // ChannelSplitterNode::new, channel_splitter.rs:146-161
+        if (n.desc.i[0] == 0) n.desc.i[0] = WAA_DEFAULT_NUMBER_OF_PORTS;
+        if (n.desc.i[0] < 1 || n.desc.i[0] > WAA_MAX_CHANNELS)
+          return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - Invalid number of channels: %d is outside range [1, %d]", n.desc.i[0], WAA_MAX_CHANNELS);
+        if (n.desc.channel_count != 0) {
+          // (a count that was "explicitly set" is one that differs from the default of 6, :152)
+          if (n.desc.channel_count != WAA_DEFAULT_NUMBER_OF_PORTS && (int)n.desc.channel_count != n.desc.i[0])
+            return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - channel count of ChannelSplitterNode must be equal to number of outputs");
+          if (n.mode != WAA_COUNT_MODE_EXPLICIT)
+            return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - channel count of ChannelSplitterNode must be set to Explicit");
+          if (n.interp != WAA_INTERP_DISCRETE)
+            return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - channel interpretation of ChannelSplitterNode must be set to Discrete");
+        }
+        n.cc = n.desc.i[0];
+        n.mode = WAA_COUNT_MODE_EXPLICIT;
+        n.interp = WAA_INTERP_DISCRETE;
+        break;
+      }
+      case WAA_NODE_CHANNEL_MERGER: {  // ChannelMergerNode::new, channel_merger.rs:122-127
+        if (n.desc.i[0] == 0) n.desc.i[0] = WAA_DEFAULT_NUMBER_OF_PORTS;
+        if (n.desc.i[0] < 1 || n.desc.i[0] > WAA_MAX_CHANNELS)
+          return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - Invalid number of channels: %d is outside range [1, %d]", n.desc.i[0], WAA_MAX_CHANNELS);
+        if (n.cc != 1) return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - channel count of ChannelMergerNode must be equal to 1");
+        if (n.mode != WAA_COUNT_MODE_EXPLICIT)
+          return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - channel count of ChannelMergerNode must be set to Explicit");
+        break;
+      }
       default: break;
     }
   }
+  // AudioNode::connect_from_output_to_input, audio_node.rs:270-279 (the nodes' port counts are known by now)
+  for (const waa_edge_desc& ed : b->edges)
+    if (int e = check_ports(b.get(), ed.from, ed.from_output, ed.to, ed.to_input)) return e;
   if (device == WAA_DEVICE_PLAN_ONLY) {
     b->dry = true;
     b->device = -1;
@@ -1290,8 +1329,9 @@ waa_status waa_render_range(waa_batch* b, uint64_t quantum0, uint32_t n_quanta) 
 
 static int check_edge(waa_batch* b, uint32_t from, uint32_t from_output, uint32_t to, uint32_t to_input) {
   if (!b) return fail(WAA_ERR_INVALID_ARGUMENT, "null batch");
-  if (from >= b->n_user_nodes || to >= b->n_user_nodes || from_output != 0 || (to_input != 0 && !(to_input & 0x80000000u)))
+  if (from >= b->n_user_nodes || to >= b->n_user_nodes)
     return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - invalid edge %u:%u -> %u:%u", from, from_output, to, to_input);
+  if (int e = check_ports(b, from, from_output, to, to_input)) return e;
   if ((to_input & 0x80000000u) && (to_input & 0x7fffffffu) >= b->nodes[to].params.size())
     return fail(WAA_ERR_INVALID_ARGUMENT, "no such param %u on node %u", to_input & 0x7fffffffu, to);
   return check_unplanned(b);
@@ -1454,6 +1494,7 @@ static int run_steps(waa_batch* b) {
       case 16: e = timed(st.profile_slot, [&] { launch_qgemm(st.qgemm, b->stream); }); break;
       case 17: e = timed(st.profile_slot, [&] { launch_hrtf(st.hrtf, b->stream); }); break;
       case 20: e = timed(st.profile_slot, [&] { launch_osfft(st.osfft, b->stream); }); break;
+      case 22: e = timed(st.profile_slot, [&] { launch_route(st.route, b->stream); }); break;  // (never inside a feedback loop)
       case 21:  // (never inside a feedback loop: always the whole render)
         if ((e = timed(st.slot_fwd, [&] { launch_compressor_level(st.comp, b->stream); }))) break;
         if ((e = timed(st.slot_mac, [&] { launch_compressor_detector(st.comp, b->stream); }))) break;

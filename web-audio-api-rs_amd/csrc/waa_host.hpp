@@ -211,6 +211,12 @@ struct Node {
   uint64_t view_valid = 0;
   // dynamic plans (waa_dyn.hip): per-quantum codes of the published signal, and the quantum slot of channel 1 when the
   // signal feeds a mono-IR convolver whose second FFTConvolver only advances on stereo quanta
+  // output ports (waa_plan_route.cpp): one NODE_SPLITTER_PORT node stands for every connected output of a ChannelSplitterNode —
+  // `port_of` = the splitter, `port` = the output; its signal is a one-channel VIEW of the splitter's input bus.  On the splitter:
+  // port_views = the bus is its only producer's signal (no launch).  silent_port: the output lies beyond the producer's channels
+  // (its only consumers are ChannelMergerNodes, which write the zeros themselves).
+  int port_of = -1, port = 0;
+  bool port_views = false, silent_port = false;
   uint8_t* code = nullptr;
   uint8_t* in_code = nullptr;  // ConvolverNode: codes of its mixed input
   uint32_t* remap = nullptr;
@@ -224,7 +230,7 @@ struct ProfileEntry {
 };
 
 struct Step {
-  int kind = 0;  // 21 DynamicsCompressorNode (level, detector, apply: waa_compressor.hip), 15 link table of a frozen-state node, 16 one resampling stage of an oversampled WaveShaper (qgemm_kernel), 17 HRTF FIR; 0 chain (interpreter kernel), 1 streaming biquad kernel, 2 FFT convolver, 3 zero-fill, 4 direct FIR, 5 per-frame biquad coefficients, 6 streaming IIR kernel, 7 delay gather, 8 feedback loop, 9 oscillator, 10 dynamic-count group (dyn_kernel), 11 convolver codes, 12 digest of a shared per-frame coefficient table, 13 per-frame panner geometry, 14 automation timelines replayed on the device
+  int kind = 0;  // 22 channel routing (route_kernel), 21 DynamicsCompressorNode (level, detector, apply: waa_compressor.hip), 15 link table of a frozen-state node, 16 one resampling stage of an oversampled WaveShaper (qgemm_kernel), 17 HRTF FIR; 0 chain (interpreter kernel), 1 streaming biquad kernel, 2 FFT convolver, 3 zero-fill, 4 direct FIR, 5 per-frame biquad coefficients, 6 streaming IIR kernel, 7 delay gather, 8 feedback loop, 9 oscillator, 10 dynamic-count group (dyn_kernel), 11 convolver codes, 12 digest of a shared per-frame coefficient table, 13 per-frame panner geometry, 14 automation timelines replayed on the device
   ChainDesc chain{};
   BiquadStreamDesc bq{};
   BiquadScanCtl scan{};   // kind 1 with scan.payload: the time-parallel form (waa_biquad_scan.hip)
@@ -244,6 +250,7 @@ struct Step {
   QGemmDesc qgemm{};
   OsFftDesc osfft{};      // kind 20: the oversampled WaveShaper in one launch (waa_osfft.hip)
   HrtfDesc hrtf{};
+  RouteDesc route{};      // kind 22: ChannelMergerNode / the input bus of a ChannelSplitterNode (waa_route.hip; reads / writes in loop_reads / loop_writes)
   CompDesc comp{};        // kind 21 (profile slots: slot_fwd = level, slot_mac = detector, slot_inv = apply)
   int slot_fwd = -1, slot_mac = -1, slot_inv = -1;
   void* zero_ptr = nullptr;
@@ -312,6 +319,10 @@ struct waa_batch {
   bool ranged = false;              // waa_render_range has been called: waa_render would render from the start again
   uint32_t n_user_nodes = 0;        // nodes of the caller's graph (the gates of timed edges are appended behind them)
   bool timed_edges_done = false;
+  bool ports_done = false;          // the outputs of ChannelSplitterNodes have been turned into port nodes (desugar_output_ports)
+  // views (one channel of another signal) by base pointer -> base of the signal that owns the memory: what a launch reads through
+  // a view is what the owner's launch writes (step_io resolves reads through it)
+  std::map<const void*, const void*> view_owner;
   std::string timed_note;
   std::vector<uint32_t> order;
   std::vector<uint8_t> cut;         // per DelayNode: writer->reader edge removed by the cycle breaker
@@ -484,6 +495,11 @@ inline bool is_frozen_node(const Node& n) {
          (n.desc.kind == WAA_NODE_PANNER && n.desc.i[0] == WAA_PANNING_HRTF);
 }
 
+// internal node kind (never in a caller's graph): one connected output of a ChannelSplitterNode (waa_plan_route.cpp)
+constexpr uint32_t NODE_SPLITTER_PORT = 0x100u;
+inline bool is_routing_node(const Node& n) {
+  return n.desc.kind == WAA_NODE_CHANNEL_SPLITTER || n.desc.kind == WAA_NODE_CHANNEL_MERGER || n.desc.kind == NODE_SPLITTER_PORT;
+}
 // DynamicsCompressorNode: rendered node-major by launches of its own (waa_compressor.hip), input and output materialised
 inline bool is_compressor(const Node& n) { return n.desc.kind == WAA_NODE_DYNAMICS_COMPRESSOR; }
 // quanta of look-ahead, in f32 exactly as dynamics_compressor.rs:253-254 sizes its ring (ring - 1)

@@ -267,6 +267,26 @@ void launch_compressor_level(const CompDesc& d, void* stream);
 void launch_compressor_detector(const CompDesc& d, void* stream);
 void launch_compressor_apply(const CompDesc& d, void* stream);
 
+// ---- ChannelSplitterNode / ChannelMergerNode (channel_splitter.rs:183-210, channel_merger.rs:145-172): waa_route.hip ----
+// Row r of the output is the sum, in connection order, of terms[row_off[r]] .. terms[row_off[r + 1] - 1]; a row without
+// terms is WRITTEN as zeros.  A term is one channel of a source signal or one of the speakers down-mixes to mono of
+// quantum.rs:387-432, each as one expression in the reference's order.
+enum : int32_t { RT_CHANNEL = 0, RT_DOWN2 = 1, RT_DOWN4 = 2, RT_DOWN6 = 3 };
+struct RouteTerm {
+  const float* base;       // channel 0 of instance 0 of the source signal
+  uint64_t inst_stride, ch_stride;
+  int32_t mode;            // RT_*
+  int32_t ch;              // RT_CHANNEL: which channel
+};
+struct RouteDesc {
+  SignalRef out;           // [n_inst][rows][frames]
+  const RouteTerm* terms;
+  const uint32_t* row_off; // [rows + 1]
+  uint32_t n_inst, rows;
+  uint64_t frames;         // padded frames per channel (a multiple of TILE)
+};
+void launch_route(const RouteDesc& d, void* stream);
+
 // ---- ConvolverNode (convolver.rs:343-490 + fft-convolver), node-major overlap-save ------------
 // out[co] = sum over terms t with t.out_ch == co of  IR[t.ir_ch] * in[t.in_ch]   (linear convolution)
 struct ConvTerm {

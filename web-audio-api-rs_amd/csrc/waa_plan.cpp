@@ -1051,6 +1051,7 @@ int source_code_rows(waa_batch* b, uint32_t id, uint64_t cs, std::vector<uint8_t
 static int build_plan_impl(waa_batch* b);
 static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vector<uint8_t>& muted);
 int build_plan(waa_batch* b) {
+  if (int e = desugar_output_ports(b)) return e;
   b->sched_cache.clear();
   const int e = build_plan_impl(b);
   b->sched_cache.clear();  // (the replays of one plan: a 10 s slow-track table is 7.7 MB)
@@ -1060,6 +1061,7 @@ int build_plan(waa_batch* b) {
 static int build_plan_impl(waa_batch* b) {
   const uint32_t N = (uint32_t)b->nodes.size();
   b->short_ring_loops.clear();
+  b->view_owner.clear();
   PlanTrace trace_total("build_plan (host + device calls)");
   std::unique_ptr<PlanTrace> ph(new PlanTrace("phase: automation + order + loops + counts"));
   if (int e = materialise_automation(b)) return e;
@@ -1254,6 +1256,12 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
     if (b->nodes[i].live && is_compressor(b->nodes[i]) && scc_of[i] >= 0)
       return fail(WAA_ERR_OUT_OF_SCOPE, "DynamicsCompressorNode %u inside a feedback loop is out of scope: its detector is rendered over the whole render "
                                         "by one launch, not quantum by quantum", i);
+  for (uint32_t i = 0; i < N; i++) {
+    const uint32_t k = b->nodes[i].desc.kind;
+    if (b->nodes[i].live && (k == WAA_NODE_CHANNEL_SPLITTER || k == WAA_NODE_CHANNEL_MERGER) && scc_of[i] >= 0)
+      return fail(WAA_ERR_OUT_OF_SCOPE, "%s %u inside a feedback loop is out of scope: the node is rendered by static plans only, over the whole render "
+                                        "by views and one launch, not quantum by quantum", k == WAA_NODE_CHANNEL_SPLITTER ? "ChannelSplitterNode" : "ChannelMergerNode", i);
+  }
   // (prepass) a modulated source that itself feeds the modulating subgraph of a modulated source: its own schedule is
   // not known before ITS modulation has been resolved — a second prepass level nobody has asked for yet; refused loudly
   // (it used to be skipped by plan_single and the outer param chain read an empty signal)
@@ -1295,6 +1303,8 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
       case WAA_NODE_OSCILLATOR: n.out_nch = 1; break;
       case WAA_NODE_STEREO_PANNER:
       case WAA_NODE_PANNER: n.out_nch = 2; break;
+      case NODE_SPLITTER_PORT: n.out_nch = 1; break;              // channel_splitter.rs:198
+      case WAA_NODE_CHANNEL_MERGER: n.out_nch = n.desc.i[0]; break;  // channel_merger.rs:160-165 (static: some input is active)
       case WAA_NODE_CONVOLVER:
         if (!n.has_ir)
           n.out_nch = n.in_nch;
@@ -1514,6 +1524,18 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
               const int64_t qs = (int64_t)q - (int64_t)compressor_delay_quanta(b->sr);
               a = qs >= 0 ? in_act[id][qs] : 0;
               c = qs >= 0 ? in_cnt[id][qs] : 1;
+            } else if (kind == NODE_SPLITTER_PORT) {
+              // channel_splitter.rs:197-206: output k is one channel — channel k of the input bus where an active connection of the
+              // splitter has one, the silent block otherwise
+              uint8_t widest = 0;
+              for (int e : b->nodes[(size_t)n.port_of].in_edges) {
+                const uint32_t p = b->edges[e].from;
+                if (act[p][q]) widest = std::max(widest, cnt[p][q]);
+              }
+              a = a && (int)widest > n.port;
+              c = 1;
+            } else if (kind == WAA_NODE_CHANNEL_MERGER) {
+              c = (uint8_t)n.desc.i[0];  // channel_merger.rs:160-168: N channels when any input is active, else one silent channel
             } else if (kind == WAA_NODE_GAIN && !zero_gain[id].empty() && zero_gain[id][q]) {
               a = 0;
             } else if (kind == WAA_NODE_WAVESHAPER && n.has_curve && !a) {
@@ -1597,6 +1619,25 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
           }
           if (wide_now) last_wide = q;
         }
+        // A ChannelMergerNode directly in front of a panner, and every input of the merger stops before the render does: the
+        // merger's output changes from N channels to the one silent channel of channel_merger.rs:166-168 mid-render, and the
+        // panning law depends on the count of its input (stereo_panner.rs / panner.rs: mono and stereo laws).  Zeros pan to
+        // zeros under either law, so this is CONSERVATIVE: the count change is reported like any other one, and the two
+        // routing nodes are static-plan only (the refusal below).
+        if (!what && (kind == WAA_NODE_PANNER || kind == WAA_NODE_STEREO_PANNER))
+          for (int e : n.in_edges) {
+            const uint32_t p = b->edges[e].from;
+            if (b->nodes[p].desc.kind != WAA_NODE_CHANNEL_MERGER || b->nodes[p].out_nch < 2) continue;
+            bool was_active = false;
+            for (uint32_t q = 0; q < nq && !what; q++) {
+              if (act[p][q]) {
+                was_active = true;
+              } else if (was_active) {
+                what = "comes from a ChannelMergerNode whose output falls back to one silent channel";
+                at = q;
+              }
+            }
+          }
         // mixing rules that do not commute with the speakers up-mix the static plan applied upstream: an input that
         // is active but narrower than its static width, into a discrete or wider-than-stereo mix
         if (!what)
@@ -1704,7 +1745,7 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
       const uint32_t ck = c.desc.kind;
       const bool other_loop = scc_of[e.to] >= 0 && !(scc_of[e.to] == scc_of[id] && block_loop(id));
       if ((e.to_input & 0x80000000u) || other_loop || (ck == WAA_NODE_CONVOLVER && c.has_ir) || is_frozen_node(c) || is_compressor(c) || c.in_nch > 2 ||
-          n.out_nch > 2)
+          n.out_nch > 2 || is_routing_node(c))
         ok = false;
     }
     if (ok && consumers > 0) folded_delay[id] = 1;
@@ -1724,6 +1765,7 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
     if (kind == WAA_NODE_DESTINATION || kind == WAA_NODE_ANALYSER || kind == WAA_NODE_CONVOLVER || kind == WAA_NODE_DELAY) mat = true;
     if (is_frozen_node(n)) mat = true;  // rendered node-major (waa_frozen.hip)
     if (is_compressor(n)) mat = true;   // rendered node-major (waa_compressor.hip)
+    if (is_routing_node(n)) mat = true; // views / one route launch (waa_plan_route.cpp)
     // (a GainNode of a block-scheduled loop may ride on an input edge of its consumer, see above)
     const bool relaxed = kind == WAA_NODE_GAIN && block_loop(id);
     if (scc_of[id] >= 0 && !relaxed) mat = true;  // loop members publish their own signal
@@ -1734,6 +1776,7 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
         live_consumers++;
         const Node& c = b->nodes[e.to];
         if ((c.desc.kind == WAA_NODE_CONVOLVER && c.has_ir) || is_frozen_node(c) || is_compressor(c)) mat = true;
+        if (is_routing_node(c)) mat = true;  // the route launch and the port views read whole signals
         if (c.desc.kind == WAA_NODE_DELAY) {
           // a DelayNode mixes its inputs like a summing chain head (node_input_signal): materialised unless foldable
           if (relaxed)
@@ -1804,7 +1847,7 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
       const Node& c = b->nodes[e.to];
       const uint32_t ck = c.desc.kind;
       if ((e.to_input & 0x80000000u) || (scc_of[e.to] >= 0 && !block_loop(e.to)) || (ck == WAA_NODE_CONVOLVER && c.has_ir) ||
-          is_frozen_node(c) || is_compressor(c) || ck == WAA_NODE_IIR_FILTER)
+          is_frozen_node(c) || is_compressor(c) || ck == WAA_NODE_IIR_FILTER || is_routing_node(c))
         shared_ok = false;
     }
     if (!shared_ok && (n_live != 1 || consumer < 0)) continue;
@@ -1998,6 +2041,13 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
       if (e) return e;
       return plan_compressor(b, id);
     }
+    if (term.desc.kind == WAA_NODE_CHANNEL_SPLITTER) {
+      bool producer_in_loop = false;
+      for (int e : term.in_edges) producer_in_loop |= scc_of[b->edges[e].from] >= 0;
+      return plan_splitter(b, id, producer_in_loop);
+    }
+    if (term.desc.kind == NODE_SPLITTER_PORT) return plan_splitter_port(b, id);
+    if (term.desc.kind == WAA_NODE_CHANNEL_MERGER) return plan_merger(b, id);
     if (is_frozen_node(term)) {
       if (scc_of[id] >= 0)
         return fail(WAA_ERR_OUT_OF_SCOPE, "an oversampled WaveShaperNode / HRTF PannerNode inside a feedback loop is out of scope (node %u)", id);
@@ -2019,7 +2069,8 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
       const uint32_t k = term.desc.kind;
       const bool identity = k == WAA_NODE_DESTINATION || k == WAA_NODE_ANALYSER ||
                             (k == WAA_NODE_CONVOLVER && !term.has_ir) || (k == WAA_NODE_WAVESHAPER && !term.has_curve);
-      if (identity && scc_of[id] < 0 && p.materialized && p.out_nch == term.in_nch && term.in_nch == term.out_nch) {
+      // (not behind an output of a ChannelSplitterNode: a view has its owner's instance stride, the destination's layout is its own)
+      if (identity && scc_of[id] < 0 && p.materialized && p.out_nch == term.in_nch && term.in_nch == term.out_nch && p.desc.kind != NODE_SPLITTER_PORT) {
         term.sig = p.sig;
         plan_note(b, "alias node %u -> output of node %u", id, b->edges[term.in_edges[0]].from);
         return 0;
@@ -2167,6 +2218,12 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
       if (b->nodes[i].live && is_compressor(b->nodes[i]))
         return fail(WAA_ERR_OUT_OF_SCOPE, "DynamicsCompressorNode %u in a graph that needs exact per-quantum channel counts (dyn_kernel) is out of scope: "
                                           "the node is rendered by static plans only", i);
+    for (uint32_t i = 0; i < N; i++) {
+      const uint32_t k = b->nodes[i].desc.kind;
+      if (b->nodes[i].live && (k == WAA_NODE_CHANNEL_SPLITTER || k == WAA_NODE_CHANNEL_MERGER))
+        return fail(WAA_ERR_OUT_OF_SCOPE, "%s %u in a graph that needs exact per-quantum channel counts (dyn_kernel) is out of scope: "
+                                          "the node is rendered by static plans only", k == WAA_NODE_CHANNEL_SPLITTER ? "ChannelSplitterNode" : "ChannelMergerNode", i);
+    }
     DynPlanCtx dc{items, units, scc_of, alloc_signal, plan_single, count_change_found, mixed_buffer_counts};
     return plan_dynamic_groups(b, dc);
   }
@@ -2236,10 +2293,10 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
         if (st.prologue && st.kind == 0) {
           // ... unless the param is modulated from INSIDE the loop: its summing chain then reads what a launch of this
           // group writes and belongs to the blocks, in its place in the order
-          const StepIo io = step_io(st);
+          const StepIo io = step_io(b, st);
           for (size_t j = first_step; j < b->steps.size() && st.prologue; j++) {
             if (j == k) continue;
-            const StepIo w = step_io(b->steps[j]);
+            const StepIo w = step_io(b, b->steps[j]);
             for (const void* r : io.reads)
               if (std::find(w.writes.begin(), w.writes.end(), r) != w.writes.end()) st.prologue = false;
           }
@@ -2305,7 +2362,7 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
           // the delayed samples are not stored: nothing but the filter may read them
           for (size_t k = 0; k < b->steps.size() && fb >= 0; k++) {
             if (k == bodies[1]) continue;
-            const StepIo io = step_io(b->steps[k]);
+            const StepIo io = step_io(b, b->steps[k]);
             if (std::find(io.reads.begin(), io.reads.end(), (const void*)rd.chain.out.base) != io.reads.end()) fb = -1;
           }
           for (const Node& an : b->nodes)

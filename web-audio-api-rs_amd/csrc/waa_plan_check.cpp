@@ -23,7 +23,20 @@ void io_input(const InputRef& in, StepIo& io) {
   if (in.kind == IN_CONSTANT) io_param(in.offset, io);
   if (in.has_gain) io_param(in.gain, io);
 }
-StepIo step_io(const Step& st) {
+// A read through a VIEW (one channel of another signal: an output of a ChannelSplitterNode, waa_plan_route.cpp) is a read of the signal
+// that owns the memory: reads are reported by the owner's base (waa_batch::view_owner), so that the read-after-write check below
+// and every fusion that asks "who else reads this signal" see them.
+static StepIo step_io_raw(const Step& st);
+StepIo step_io(const waa_batch* b, const Step& st) {
+  StepIo io = step_io_raw(st);
+  if (!b->view_owner.empty())
+    for (const void*& r : io.reads) {
+      auto it = b->view_owner.find(r);
+      if (it != b->view_owner.end()) r = it->second;
+    }
+  return io;
+}
+static StepIo step_io_raw(const Step& st) {
   StepIo io;
   switch (st.kind) {
     case 0: {
@@ -105,6 +118,7 @@ StepIo step_io(const Step& st) {
       io.writes.push_back(st.delay.out.base);
       io.feedback_reader = st.delay.in_cycle != 0;
       break;
+    case 22:  // (the terms of a route launch: recorded by the planner, views resolved)
     case 8:
     case 10:
     case 16:
@@ -128,7 +142,7 @@ int validate_plan(waa_batch* b) {
   std::vector<StepIo> ios;
   std::set<const void*> produced, written;
   for (const Step& st : b->steps) {
-    ios.push_back(step_io(st));
+    ios.push_back(step_io(b, st));
     for (const void* w : ios.back().writes)
       if (w) produced.insert(w);
   }

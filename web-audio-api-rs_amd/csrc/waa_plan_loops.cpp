@@ -29,7 +29,7 @@ static void fuse_filtered_echo_tail(waa_batch* b, size_t l) {
     if (k == l) continue;
     const Step& sk = b->steps[k];
     if (sk.echo_fused && sk.group == ls.group) continue;  // (the delayed read and the filter: inside the launch)
-    const StepIo io = step_io(sk);
+    const StepIo io = step_io(b, sk);
     auto delayed_from = [&](const InputRef& in) { return in.kind == IN_DELAYED && in.sig.base == line; };
     bool rl = std::find(io.reads.begin(), io.reads.end(), line) != io.reads.end();
     if (sk.kind == 0)
@@ -90,7 +90,7 @@ void fuse_echo_tails(waa_batch* b) {
     for (size_t k = 0; k < b->steps.size(); k++) {
       if (k == l) continue;
       const Step& sk = b->steps[k];
-      const StepIo io = step_io(sk);
+      const StepIo io = step_io(b, sk);
       // (a delayed read marked `feedback` is left out of the read sets: the validation's legal read-before-write)
       auto delayed_from = [&](const InputRef& in) { return in.kind == IN_DELAYED && in.sig.base == line; };
       bool reads = std::find(io.reads.begin(), io.reads.end(), line) != io.reads.end();

@@ -402,6 +402,15 @@ void default_channel_config(Node& n, uint32_t n_out) {
     case WAA_NODE_DYNAMICS_COMPRESSOR:
       mode = WAA_COUNT_MODE_CLAMPED_MAX;
       break;
+    case WAA_NODE_CHANNEL_SPLITTER:  // ChannelSplitterOptions::default, channel_splitter.rs:90-101 (the count follows number_of_outputs)
+      cc = n.desc.i[0] >= 1 && n.desc.i[0] <= WAA_MAX_CHANNELS ? n.desc.i[0] : WAA_DEFAULT_NUMBER_OF_PORTS;  // (out of range: refused by waa_batch_create)
+      mode = WAA_COUNT_MODE_EXPLICIT;
+      interp = WAA_INTERP_DISCRETE;
+      break;
+    case WAA_NODE_CHANNEL_MERGER:  // ChannelMergerOptions::default, channel_merger.rs:72-83
+      cc = 1;
+      mode = WAA_COUNT_MODE_EXPLICIT;
+      break;
     default: break;
   }
   if (n.desc.channel_count != 0) {

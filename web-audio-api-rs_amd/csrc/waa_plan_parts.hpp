@@ -56,7 +56,7 @@ int source_code_rows(waa_batch* b, uint32_t id, uint64_t cs, std::vector<uint8_t
 int build_plan(waa_batch* b);
 void io_param(const ParamRef& p, StepIo& io);
 void io_input(const InputRef& in, StepIo& io);
-StepIo step_io(const Step& st);
+StepIo step_io(const waa_batch* b, const Step& st);  // (reads through a view are reported by the owning signal, b->view_owner)
 int validate_plan(waa_batch* b);
 void fuse_echo_tails(waa_batch* b);
 void ring_feed_forward_echoes(waa_batch* b);
@@ -80,6 +80,11 @@ int conv_block_size(const waa_batch* b, const Node& n);
 bool conv_fold_biquad_into_ir(const waa_batch* b, Node& conv, const Node& q);
 int plan_convolver(waa_batch* b, uint32_t id);
 int plan_compressor(waa_batch* b, uint32_t id);
+// waa_plan_route.cpp: ChannelSplitterNode / ChannelMergerNode
+int desugar_output_ports(waa_batch* b);
+int plan_splitter(waa_batch* b, uint32_t id, bool producer_in_loop);
+int plan_splitter_port(waa_batch* b, uint32_t id);
+int plan_merger(waa_batch* b, uint32_t id);
 int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector<OpDesc>& ops, int* out_nch);
 void default_channel_config(Node& n, uint32_t n_out);
 

@@ -546,11 +546,11 @@ void fuse_fm_operators(waa_batch* b) {
     bool shared = false;
     for (size_t k = 0; k < b->steps.size() && !shared; k++) {
       if ((int)k == pi || k == c) continue;
-      const StepIo io = step_io(b->steps[k]);
+      const StepIo io = step_io(b, b->steps[k]);
       for (const void* r : io.reads) shared |= r == table || ((int)k != pi && r == (const void*)ms.osc.out.base);
     }
     {
-      const StepIo io = step_io(cs);  // (the carrier itself: its detune could be modulated from the same oscillator)
+      const StepIo io = step_io(b, cs);  // (the carrier itself: its detune could be modulated from the same oscillator)
       for (const void* r : io.reads) shared |= r == (const void*)ms.osc.out.base;
     }
     for (const Node& an : b->nodes)
@@ -605,7 +605,7 @@ void fuse_lfo_params(waa_batch* b) {
     bool shared = false;
     for (size_t k = 0; k < b->steps.size() && !shared; k++) {
       if (k == pi) continue;
-      const StepIo io = step_io(b->steps[k]);
+      const StepIo io = step_io(b, b->steps[k]);
       for (const void* r : io.reads) shared |= r == (const void*)ms.osc.out.base;
     }
     for (const Node& an : b->nodes)
