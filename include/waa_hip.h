@@ -149,6 +149,16 @@ enum {
  *     ANALYSER    i[0] = fft_size, d[0] smoothing_time_constant, d[1] min_decibels, d[2] max_decibels
  *     WAVESHAPER  i[0] = oversample
  *     CONVOLVER   i[0] = disable_normalization (0/1)
+ *                 i[1] = 0: one impulse response for the whole batch; 1: one impulse response per instance — every
+ *                 OfflineAudioContext of the reference owns its ConvolverNode and its buffer.  With i[1] = 1
+ *                 waa_convolver_set_buffer reads n_instances x n_channels pointers (see there), the normalisation
+ *                 (i[0] == 0) runs once per instance over that instance's channels, and a node without a buffer passes
+ *                 its input through, as with i[1] = 0.  n_channels, frames and sample_rate are common to the batch: a
+ *                 caller whose responses differ in length pads them with zeros to `frames`.  The reference's RMS
+ *                 (convolver.rs:16-53) then sees the PADDED length; a caller who wants the scale of the unpadded
+ *                 response disables the normalisation (i[0] = 1) and scales the response itself.  Static plans only:
+ *                 WAA_ERR_OUT_OF_SCOPE inside a feedback loop and in a graph that needs exact per-quantum channel
+ *                 counts; waa_convolver_set_buffer_pcm16 on such a node is WAA_ERR_OUT_OF_SCOPE.
  *     OSCILLATOR  i[0] = type (WAA_OSC_*; CUSTOM needs waa_oscillator_set_periodic_wave); scheduled with
  *                 waa_source_start / waa_source_stop like the other AudioScheduledSourceNodes
  *     CHANNEL_SPLITTER  i[0] = number_of_outputs (0 = the default, 6; [1, 32]: IndexSizeError, channel_splitter.rs:23-30).
@@ -284,7 +294,13 @@ waa_status waa_convolver_set_buffer_pcm16(waa_batch* batch, uint32_t node, const
                                           uint64_t frames, float sample_rate);
 
 /* Impulse response shared by all instances. sample_rate must equal the context's
- * (NotSupportedError otherwise), n_channels in {1,2,4}. */
+ * (NotSupportedError otherwise), n_channels in {1,2,4}.
+ * On a node created with i[1] = 1 (one impulse response per instance, see waa_node_desc) `channels` holds
+ * n_instances x n_channels pointers indexed [instance][channel], each at `frames` f32; n_channels, frames and sample_rate
+ * are common to the batch.  A NULL pointer: WAA_ERR_INVALID_ARGUMENT naming the instance and the channel.  The
+ * normalisation runs per instance; responses of different lengths are zero-padded to `frames` by the caller, the
+ * normalisation then sees the padded length (disable it and scale the response yourself for the unpadded value).
+ * waa_batch_rearm keeps the responses, like everything but the audio. */
 waa_status waa_convolver_set_buffer(waa_batch* batch, uint32_t node, const float* const* channels,
                                     uint32_t n_channels, uint64_t frames, float sample_rate);
 waa_status waa_waveshaper_set_curve(waa_batch* batch, uint32_t node, const float* curve, uint32_t n);
@@ -444,7 +460,9 @@ typedef struct waa_sharded_job {
                                   * has been downloaded is re-armed (waa_batch_rearm) for a later sub-batch of the same size instead
                                   * of being destroyed — the later one skips creation, setup and planning.  Ignored (every
                                   * sub-batch is created anew) when the graph has an edge into an AudioParam: its plan may hold
-                                  * values rendered from the sub-batch's own audio (waa_batch_rearm) */
+                                  * values rendered from the sub-batch's own audio (waa_batch_rearm).  A `setup` that hands
+                                  * every sub-batch its own slice [first, first + count) of per-instance impulse responses
+                                  * (CONVOLVER i[1] = 1) depends on `first`: leave this 0 there */
 } waa_sharded_job;
 /* Blocks until every context is rendered and downloaded; *seconds (may be NULL) = wall time.  Pinned host buffers let
  * the transfers run at link speed, and a device arena (waa_device_arena_reserve, once per process) keeps hipMalloc / hipFree —

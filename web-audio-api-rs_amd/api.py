@@ -736,6 +736,7 @@ class ConvolverNode(AudioNode):
         super().__init__(ctx, **kw)
         self.normalize = not disable_normalization
         self.buffer = None
+        self._inst_buffers = {}  # instance -> AudioBuffer: one impulse response per context (waa_node_desc.i[1] = 1)
         self._normalize_at_set = self.normalize
         if buffer is not None:
             self.set_buffer(buffer)
@@ -743,14 +744,54 @@ class ConvolverNode(AudioNode):
     def set_normalize(self, value: bool):
         self.normalize = bool(value)
 
-    def set_buffer(self, buffer: AudioBuffer):
+    def set_buffer(self, buffer: AudioBuffer, instance: int = ALL):
+        """instance = ALL: the impulse response of every context.  instance = i: context i's own response — every context of
+        the reference owns its ConvolverNode and its buffer.  As soon as one instance has its own response the node works in
+        per-instance mode; instances without one use the ALL buffer.  All responses of a node share channel count and length
+        (pad shorter ones with zeros; the normalisation then sees the padded length)."""
         if buffer.sample_rate != self.context.sample_rate:
             raise WaaError(2, "NotSupportedError - sample rate of the convolution buffer must match the audio context")
         if buffer.number_of_channels not in (1, 2, 4):
             raise WaaError(2, "NotSupportedError - the convolution buffer must consist of 1, 2 or 4 channels")
-        self.buffer = buffer
+        if instance == ALL:
+            self.buffer = buffer
+        else:
+            if not 0 <= int(instance) < self.context.n_instances:
+                raise WaaError(1, f"instance {instance} out of range")
+            self._inst_buffers[int(instance)] = buffer
         self._normalize_at_set = self.normalize
         return self
+
+    def set_buffer_batch(self, data, sample_rate: float):
+        """data: [n_instances, channels, frames] — one impulse response per context."""
+        data = _f32(data)
+        if data.ndim != 3 or data.shape[0] != self.context.n_instances:
+            raise WaaError(1, f"set_buffer_batch takes [n_instances = {self.context.n_instances}, channels, frames], got {data.shape}")
+        for i in range(data.shape[0]):
+            self.set_buffer(AudioBuffer(data[i], sample_rate), instance=i)
+        return self
+
+    @property
+    def per_instance(self) -> bool:
+        return bool(self._inst_buffers)
+
+    def _instance_buffers(self):
+        """The response of every context in per-instance mode; WaaError(4) for what the batch cannot express."""
+        if self.context._b.prefix != "waa_":
+            raise WaaError(4, "one impulse response per instance is a feature of the device library; this binding keeps one response "
+                              "per batch (render it one context at a time)")
+        bufs = [self._inst_buffers.get(i, self.buffer) for i in range(self.context.n_instances)]
+        for i, bf in enumerate(bufs):
+            if bf is None:
+                raise WaaError(4, f"ConvolverNode in per-instance mode: instance {i} has no impulse response (set one for it, or one for ALL)")
+        for i, bf in enumerate(bufs):
+            if bf.number_of_channels != bufs[0].number_of_channels:
+                raise WaaError(4, f"per-instance impulse responses must share the channel count: instance {i} has "
+                                  f"{bf.number_of_channels}, instance 0 has {bufs[0].number_of_channels}")
+            if bf.length != bufs[0].length:
+                raise WaaError(4, f"per-instance impulse responses must share the length (pad with zeros): instance {i} has "
+                                  f"{bf.length} frames, instance 0 has {bufs[0].length}")
+        return bufs
 
     def set_buffer_pcm16(self, pcm, sample_rate: float):
         """decode_audio_data_sync + set_buffer: pcm = [frames, channels] int16 at `sample_rate`; decoded and resampled to
@@ -764,8 +805,22 @@ class ConvolverNode(AudioNode):
 
     def _fill_desc(self, d):
         d.i[0] = 0 if self._normalize_at_set else 1
+        if self.per_instance:
+            self._instance_buffers()  # (refusals before the batch exists)
+            d.i[1] = 1
 
     def _apply(self, ctx):
+        if self.per_instance:
+            if getattr(self, "_pcm", None) is not None:
+                raise WaaError(4, "16-bit impulse responses per instance are out of scope")
+            bufs = self._instance_buffers()
+            nch = bufs[0].number_of_channels
+            table = (_FP * (len(bufs) * nch))()  # [instance][channel]
+            for i, bf in enumerate(bufs):
+                for c in range(nch):
+                    table[i * nch + c] = bf.data[c].ctypes.data_as(_FP)
+            ctx._b.check(ctx._b.convolver_set_buffer(ctx._handle, self.id, table, nch, bufs[0].length, bufs[0].sample_rate))
+            return
         if getattr(self, "_pcm", None) is not None:
             pcm, sr = self._pcm
             ctx._b.check(ctx._b.convolver_set_buffer_pcm16(ctx._handle, self.id, pcm.ctypes.data_as(C.POINTER(C.c_int16)),

@@ -159,6 +159,8 @@ waa_status waa_batch_create(const waa_graph_desc* g, uint32_t n_inst, uint32_t n
           return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - ConvolverNode channel count cannot be greater than two");
         if (n.mode == WAA_COUNT_MODE_MAX)
           return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - ConvolverNode channel count mode cannot be set to max");
+        if (n.desc.i[1] != 0 && n.desc.i[1] != 1)
+          return fail(WAA_ERR_INVALID_ARGUMENT, "ConvolverNode: i[1] is 0 (one impulse response per batch) or 1 (one per instance), got %d", n.desc.i[1]);
         break;
       case WAA_NODE_DYNAMICS_COMPRESSOR: {  // dynamics_compressor.rs:182-247 (and :72-96 for the two constraints)
         if (n.cc > 2)
@@ -737,6 +739,29 @@ waa_status waa_convolver_set_buffer(waa_batch* b, uint32_t node, const float* co
   if (!(n_ch == 1 || n_ch == 2 || n_ch == 4))
     return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - the convolution buffer must consist of 1, 2 or 4 channels");
   Node& n = b->nodes[node];
+  if (n.per_inst_ir()) {
+    // one impulse response per instance: `channels` is the table [instance][channel]; normalize_buffer runs per instance over
+    // that instance's channels, like the ConvolverNode of every context of the reference
+    if (!channels) return fail(WAA_ERR_INVALID_ARGUMENT, "ConvolverNode %u: the table of per-instance impulse responses is NULL", node);
+    for (uint32_t i = 0; i < b->n_inst; i++)
+      for (uint32_t c = 0; c < n_ch; c++)
+        if (!channels[(size_t)i * n_ch + c] && frames)
+          return fail(WAA_ERR_INVALID_ARGUMENT, "ConvolverNode %u: the impulse response of instance %u, channel %u is NULL", node, i, c);
+    n.ir.clear();
+    n.ir_len = frames;
+    n.ir_nch = (int)n_ch;
+    n.ir_inst.assign((size_t)b->n_inst * n_ch * frames, 0.f);
+    for (uint32_t i = 0; i < b->n_inst; i++) {
+      const float* const* chs = channels + (size_t)i * n_ch;
+      const float scale = n.desc.i[0] ? 1.f : normalize_buffer(chs, n_ch, frames, sr);
+      for (uint32_t c = 0; c < n_ch; c++) {
+        float* dst = n.ir_inst.data() + ((size_t)i * n_ch + c) * frames;
+        for (uint64_t f = 0; f < frames; f++) dst[f] = chs[c][f] * scale;
+      }
+    }
+    n.has_ir = true;
+    return WAA_OK;
+  }
   const float scale = n.desc.i[0] ? 1.f : normalize_buffer(channels, n_ch, frames, sr);
   n.ir.assign(n_ch, std::vector<float>(frames));
   for (uint32_t c = 0; c < n_ch; c++)
@@ -753,6 +778,9 @@ waa_status waa_convolver_set_buffer_pcm16(waa_batch* b, uint32_t node, const int
                                           float sr) {
   int e;
   if ((e = check_node(b, node, WAA_NODE_CONVOLVER)) || (e = check_unplanned(b))) return e;
+  if (b->nodes[node].per_inst_ir())
+    return fail(WAA_ERR_OUT_OF_SCOPE, "ConvolverNode %u takes one impulse response per instance (i[1] = 1): 16-bit responses are out of scope "
+                                      "there, decode them and call waa_convolver_set_buffer", node);
   if (!(n_ch == 1 || n_ch == 2 || n_ch == 4))
     return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - the convolution buffer must consist of 1, 2 or 4 channels");
   if (!(sr >= 3000.f && sr <= 768000.f)) return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - Invalid sample rate: %f", sr);
@@ -1456,7 +1484,7 @@ static int run_steps(waa_batch* b) {
         d.kb1 = (int)std::min<uint64_t>(((uint64_t)t1 * TILE + (uint64_t)d.block - 1) / (uint64_t)d.block, (uint64_t)d.nb);
         if (d.kb1 <= d.kb0) break;
         if ((e = timed(st.slot_fwd, [&] { launch_conv_forward(d, b->stream); }))) break;
-        if ((e = timed(st.slot_mac, [&] { launch_conv_mac(d, b->stream); }))) break;
+        if ((e = timed(st.slot_mac, [&] { d.per_inst ? launch_conv_inst_mac(d, b->stream) : launch_conv_mac(d, b->stream); }))) break;
         e = timed(st.slot_inv, [&] { launch_conv_inverse(d, b->stream); });
         break;
       }
@@ -1466,7 +1494,7 @@ static int run_steps(waa_batch* b) {
         d.kb0 = (int)std::min<uint64_t>((uint64_t)t0 * (TILE / 1024), (uint64_t)st.conv.kb1);
         d.kb1 = (int)std::min<uint64_t>((uint64_t)t1 * (TILE / 1024), (uint64_t)st.conv.kb1);
         if (d.kb1 <= d.kb0) break;
-        e = timed(st.slot_mac, [&] { launch_conv_direct(d, b->stream); });
+        e = timed(st.slot_mac, [&] { d.per_inst ? launch_conv_inst_direct(d, b->stream) : launch_conv_direct(d, b->stream); });
         break;
       }
       case 5: e = timed(st.profile_slot, [&] { launch_biquad_coefs(st.coef, b->stream); }); break;

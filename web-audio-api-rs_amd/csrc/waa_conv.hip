@@ -225,14 +225,15 @@ __global__ void conv_fft_kernel(const ConvDesc d) {
   const uint32_t pair = blockIdx.z;
   if (MODE == MODE_IR) {
     // spectrum of IR partition k of IR channel c: h[kB .. (k+1)B) zero-padded to 2B
-    const float* h = d.ir + (uint64_t)c * d.ir_len;
+    // (blockIdx.z: the instance of a per-instance response, waa_conv_inst.hip; 0 with a stride of 0 for the shared one)
+    const float* h = d.ir + (uint64_t)pair * d.ir_inst_stride + (uint64_t)c * d.ir_len;
     for (int i = tid; i < n; i += nt) {
       const uint64_t idx = (uint64_t)k * B + i;
       a[pad(i)] = Cplx{(i < B && idx < d.ir_len) ? h[idx] : 0.f, 0.f};
     }
     __syncthreads();
     fft_dif_padded(a, d.tw, n, tid, nt);
-    Cplx* dst = const_cast<Cplx*>(d.H) + ((uint64_t)c * d.parts + k) * n;
+    Cplx* dst = const_cast<Cplx*>(d.H) + (((uint64_t)pair * d.ir_nch + c) * d.parts + k) * n;
     for (int i = tid; i < n; i += nt) dst[i] = a[pad(i)];
     return;
   }
@@ -938,8 +939,8 @@ static void allow_big_lds(size_t bytes) {
 void launch_conv_ir_spectra(const ConvDesc& d, void* stream) {
   if (d.fft3) return launch_conv3_ir_spectra(d, stream);
   allow_big_lds((size_t)d.n * sizeof(Cplx));
-  hipLaunchKernelGGL(conv_fft_kernel<MODE_IR>, dim3(d.parts, d.ir_nch, 1), dim3(fft_threads(d.n)), (size_t)(d.n + d.n / 8) * sizeof(Cplx),
-                     (hipStream_t)stream, d);
+  hipLaunchKernelGGL(conv_fft_kernel<MODE_IR>, dim3(d.parts, d.ir_nch, d.per_inst ? d.n_inst : 1), dim3(fft_threads(d.n)),
+                     (size_t)(d.n + d.n / 8) * sizeof(Cplx), (hipStream_t)stream, d);
 }
 // blocks per persistent workgroup: whole (pair, channel) streams when there are enough of them to fill the chip,
 // shorter runs otherwise

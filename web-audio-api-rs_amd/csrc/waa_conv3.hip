@@ -83,7 +83,9 @@ __global__ __launch_bounds__(NT) void conv_fft3_fwd_kernel(const ConvDesc d, int
   if (MODE == F3_IR) {
     // spectrum of IR partition k of IR channel c: h[kB .. (k+1)B) zero-padded to 2B, imaginary part 0
     const int k = blockIdx.x, c = blockIdx.y;
-    const float* h = d.ir + (uint64_t)c * d.ir_len;
+    // (blockIdx.z: the instance of a per-instance response, waa_conv_inst.hip; 0 with a stride of 0 for the shared one)
+    const uint32_t inst = blockIdx.z;
+    const float* h = d.ir + (uint64_t)inst * d.ir_inst_stride + (uint64_t)c * d.ir_len;
     c2v x[32];
 #pragma unroll
     for (int j = 0; j < 16; j++) {
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(NT) void conv_fft3_fwd_kernel(const ConvDesc d, int
     f3_barrier();
     fwd_pass2_write(x, lds, t);
     f3_barrier();
-    c2v* dst = reinterpret_cast<c2v*>(const_cast<Cplx*>(d.H)) + ((uint64_t)c * d.parts + k) * N;
+    c2v* dst = reinterpret_cast<c2v*>(const_cast<Cplx*>(d.H)) + (((uint64_t)inst * d.ir_nch + c) * d.parts + k) * N;
 #pragma unroll
     for (int set = 0; set < 2; set++) {
       const int r = t + set * NT;
@@ -604,7 +606,7 @@ static int f3_blocks_per_wg(const ConvDesc& d, int channels) {
 
 void launch_conv3_ir_spectra(const ConvDesc& d, void* stream) {
   f3_allow_lds();
-  hipLaunchKernelGGL(conv_fft3_fwd_kernel<F3_IR>, dim3(d.parts, d.ir_nch, 1), dim3(NT), (size_t)LDS_BYTES, (hipStream_t)stream, d, 1);
+  hipLaunchKernelGGL(conv_fft3_fwd_kernel<F3_IR>, dim3(d.parts, d.ir_nch, d.per_inst ? d.n_inst : 1), dim3(NT), (size_t)LDS_BYTES, (hipStream_t)stream, d, 1);
 }
 void launch_conv3_forward(const ConvDesc& d, void* stream) {
   f3_allow_lds();

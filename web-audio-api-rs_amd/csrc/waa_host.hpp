@@ -157,6 +157,11 @@ struct Node {
   uint64_t ir_len = 0;
   int ir_nch = 0;
   bool has_ir = false;
+  // one impulse response per instance (desc.i[1] = 1): host copy, scaled per instance, flat [inst][ch][frame] with ir_nch channels
+  // of ir_len frames each; `ir` stays empty then (it is the shared response's storage)
+  std::vector<float> ir_inst;
+  bool per_inst_ir() const { return desc.kind == WAA_NODE_CONVOLVER && desc.i[1] == 1; }
+  const float* ir_of(uint32_t inst, int ch) const { return ir_inst.data() + ((size_t)inst * (size_t)ir_nch + (size_t)ch) * ir_len; }
   // the impulse response with the transfer function of the Biquad in front folded in (conv_fold_biquad_into_ir); empty = not folded
   std::vector<std::vector<float>> ir_lti;
   uint64_t ir_lti_len = 0;

@@ -326,6 +326,11 @@ struct ConvDesc {
   const double* pre_coefs;   // [n_inst][pre_coef_stride]: b0 b1 b2 a1 a2 (null: no filter)
   uint64_t pre_coef_stride;
   double* pre_state;         // [n_inst][STATE_STRIDE]: x1 x2 y1 y2 per channel (initial state in, final state out)
+  // One impulse response per instance (waa_node_desc.i[1] = 1; waa_conv_inst.hip): `ir` is [n_inst][ir_nch][ir_len] and `H`
+  // [n_inst][ir_nch][P][n]; instance i's data lies i * ir_inst_stride floats / i * ir_nch * P * n spectra behind instance 0's.
+  // per_inst = 0 (and ir_inst_stride = 0): the shared response, everything above as it was.
+  uint64_t ir_inst_stride;
+  int32_t per_inst, pad3;
 };
 struct AnalyserDesc {
   SignalRef sig;         // the analyser's (passthrough) signal
@@ -358,6 +363,10 @@ void launch_conv_inverse(const ConvDesc& d, void* stream);
 void launch_conv3_ir_spectra(const ConvDesc& d, void* stream);
 void launch_conv3_forward(const ConvDesc& d, void* stream);
 void launch_conv3_inverse(const ConvDesc& d, void* stream);
+// waa_conv_inst.hip (d.per_inst): the direct FIR with every instance's own taps, and the product of pair spectra Z = A + iB with
+// two different responses (the transforms in front of and behind it are the shared path's)
+void launch_conv_inst_direct(const ConvDesc& d, void* stream);
+void launch_conv_inst_mac(const ConvDesc& d, void* stream);
 
 // ---- DelayNode outside a cycle (delay.rs:428-745) as a gather from its materialised input ---------
 struct DelayDesc {

@@ -1262,6 +1262,10 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
       return fail(WAA_ERR_OUT_OF_SCOPE, "%s %u inside a feedback loop is out of scope: the node is rendered by static plans only, over the whole render "
                                         "by views and one launch, not quantum by quantum", k == WAA_NODE_CHANNEL_SPLITTER ? "ChannelSplitterNode" : "ChannelMergerNode", i);
   }
+  for (uint32_t i = 0; i < N; i++)
+    if (b->nodes[i].live && b->nodes[i].per_inst_ir() && b->nodes[i].has_ir && scc_of[i] >= 0)
+      return fail(WAA_ERR_OUT_OF_SCOPE, "ConvolverNode %u with one impulse response per instance inside a feedback loop is out of scope: "
+                                        "per-instance responses are rendered by static plans outside loops only", i);
   // (prepass) a modulated source that itself feeds the modulating subgraph of a modulated source: its own schedule is
   // not known before ITS modulation has been resolved — a second prepass level nobody has asked for yet; refused loudly
   // (it used to be skipped by plan_single and the outer param chain read an empty signal)
@@ -2224,6 +2228,10 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
         return fail(WAA_ERR_OUT_OF_SCOPE, "%s %u in a graph that needs exact per-quantum channel counts (dyn_kernel) is out of scope: "
                                           "the node is rendered by static plans only", k == WAA_NODE_CHANNEL_SPLITTER ? "ChannelSplitterNode" : "ChannelMergerNode", i);
     }
+    for (uint32_t i = 0; i < N; i++)
+      if (b->nodes[i].live && b->nodes[i].per_inst_ir() && b->nodes[i].has_ir)
+        return fail(WAA_ERR_OUT_OF_SCOPE, "ConvolverNode %u with one impulse response per instance in a graph that needs exact per-quantum channel "
+                                          "counts (dyn_kernel) is out of scope: per-instance responses are rendered by static plans only", i);
     DynPlanCtx dc{items, units, scc_of, alloc_signal, plan_single, count_change_found, mixed_buffer_counts};
     return plan_dynamic_groups(b, dc);
   }

@@ -9,15 +9,27 @@
 namespace waa {
 namespace host {
 
+// length of one channel of an impulse response without its trailing |h| < 1e-6 samples (fft-convolver init)
+static uint64_t conv_trimmed(const float* h, uint64_t l) {
+  while (l > 0 && std::fabs(h[l - 1]) < 0.000001f) l--;
+  return l;
+}
+// the longest trimmed channel of the node's impulse response(s): over the channels, and over the instances of a per-instance node
+static uint64_t conv_longest_trim(const waa_batch* b, const Node& n) {
+  uint64_t len = 0;
+  if (n.per_inst_ir()) {
+    for (uint32_t i = 0; i < b->n_inst; i++)
+      for (int c = 0; c < n.ir_nch; c++) len = std::max(len, conv_trimmed(n.ir_of(i, c), n.ir_len));
+  } else {
+    for (int c = 0; c < n.ir_nch; c++) len = std::max(len, conv_trimmed(n.ir[c].data(), n.ir_len));
+  }
+  return len;
+}
+
 // the partition size the FFT path picks for a node's impulse response (0: none / all-zero / direct FIR)
 int conv_block_size(const waa_batch* b, const Node& n) {
   if (!n.has_ir) return 0;
-  uint64_t len = 0;
-  for (int c = 0; c < n.ir_nch; c++) {
-    uint64_t l = n.ir_len;
-    while (l > 0 && std::fabs(n.ir[c][l - 1]) < 0.000001f) l--;
-    len = std::max(len, l);
-  }
+  const uint64_t len = conv_longest_trim(b, n);
   if (len == 0) return 0;
   if (len <= (uint64_t)DIRECT_MAX_TAPS && !b->dynamic && !measure_switch("WAA_NO_DIRECT_FIR")) return 0;
   for (int cand : {128, 512, 2048, 8192})
@@ -45,6 +57,7 @@ bool conv_fold_biquad_into_ir(const waa_batch* b, Node& conv, const Node& q) {
   // samples and who needs the reference's recovery from them sets WAA_NO_CONV_BIQUAD_IR_FOLD=1 and gets the exact-order filter
   // stage of conv_fft3_fwd_bq_kernel back; DESIGN.md section 5.9, INTEGRATION.md "runtime switches")
   if (getenv("WAA_NO_CONV_BIQUAD_IR_FOLD") || !conv.has_ir || q.params.size() < 4) return false;  // (read per plan: tests toggle it)
+  if (conv.per_inst_ir()) return false;  // (one response per context: the fold into the forward transform does not look at H)
   float pv[4];
   for (int k = 0; k < 4; k++) {
     const ParamStore& ps = q.params[k];
@@ -129,19 +142,13 @@ int plan_convolver(waa_batch* b, uint32_t id) {
   // one FFTConvolver per IR channel, at least two (convolver.rs:291-306); each trims its own trailing
   // |h| < 1e-6 samples (fft-convolver init) — only the longest trimmed length matters here
   const int ir_nch = n.ir_nch;
-  const bool lti = n.pre_biquad >= 0 && n.ir_lti_len > 0;  // the Biquad in front lives in the impulse response
+  const bool per_inst = n.per_inst_ir();  // one impulse response per instance (waa_conv_inst.hip)
+  const bool lti = !per_inst && n.pre_biquad >= 0 && n.ir_lti_len > 0;  // the Biquad in front lives in the impulse response
   const std::vector<std::vector<float>>& ir_use = lti ? n.ir_lti : n.ir;
   const uint64_t ir_use_len = lti ? n.ir_lti_len : n.ir_len;
-  uint64_t len = 0;
-  if (lti) {
-    len = n.ir_lti_len;  // (already cut where the folded response ends)
-  } else {
-    for (int c = 0; c < ir_nch; c++) {
-      uint64_t l = n.ir_len;
-      while (l > 0 && std::fabs(n.ir[c][l - 1]) < 0.000001f) l--;
-      len = std::max(len, l);
-    }
-  }
+  // (per instance: the longest trimmed channel of ANY instance decides the block size, the partitions and the kernel — the
+  // batch is one launch; every channel of every instance still drops what lies behind its own trim, below)
+  const uint64_t len = lti ? n.ir_lti_len /* (already cut where the folded response ends) */ : conv_longest_trim(b, n);
   Step st;
   st.kind = 2;
   ConvDesc& cv = st.conv;
@@ -186,6 +193,8 @@ int plan_convolver(waa_batch* b, uint32_t id) {
   cv.ir_len = len;
   cv.kb0 = 0;
   cv.kb1 = direct_fir ? (int)((b->lp + 1023) / 1024) : cv.nb;  // (the direct kernel works in 1024-frame pieces)
+  cv.per_inst = per_inst ? 1 : 0;
+  cv.ir_inst_stride = per_inst ? (uint64_t)ir_nch * len : 0;
   // routing (convolver.rs:384-466)
   auto term = [&](int in_ch, int ir_ch, int out_ch) { cv.terms[cv.n_terms++] = ConvTerm{in_ch, ir_ch, out_ch, 0}; };
   if (n.in_nch == 1 && ir_nch == 1) {
@@ -211,12 +220,22 @@ int plan_convolver(waa_batch* b, uint32_t id) {
     term(0, 3, 1);
   }
   // device resources
-  std::vector<float> irflat((size_t)ir_nch * len);
-  for (int c = 0; c < ir_nch; c++) {
-    uint64_t l = ir_use_len;
-    if (!lti)
-      while (l > 0 && std::fabs(ir_use[c][l - 1]) < 0.000001f) l--;  // samples past a channel's own trim are dropped
-    for (uint64_t i = 0; i < len; i++) irflat[(size_t)c * len + i] = i < l ? ir_use[c][i] : 0.f;
+  std::vector<float> irflat((size_t)(per_inst ? b->n_inst : 1) * ir_nch * len);
+  if (per_inst) {
+    for (uint32_t inst = 0; inst < b->n_inst; inst++)
+      for (int c = 0; c < ir_nch; c++) {
+        const float* h = n.ir_of(inst, c);
+        const uint64_t l = conv_trimmed(h, n.ir_len);  // (an all-zero instance or channel: zeros, its output is zero)
+        float* dst = irflat.data() + ((size_t)inst * ir_nch + c) * len;
+        for (uint64_t i = 0; i < len; i++) dst[i] = i < l ? h[i] : 0.f;
+      }
+  } else {
+    for (int c = 0; c < ir_nch; c++) {
+      uint64_t l = ir_use_len;
+      if (!lti)
+        while (l > 0 && std::fabs(ir_use[c][l - 1]) < 0.000001f) l--;  // samples past a channel's own trim are dropped
+      for (uint64_t i = 0; i < len; i++) irflat[(size_t)c * len + i] = i < l ? ir_use[c][i] : 0.f;
+    }
   }
   float* d_ir = nullptr;
   int e = dev_upload(b, &d_ir, irflat);
@@ -224,10 +243,10 @@ int plan_convolver(waa_batch* b, uint32_t id) {
   cv.ir = d_ir;
   if (direct_fir) {
     st.kind = 4;
-    st.slot_mac = slot_for(b, "conv_direct_kernel");
+    st.slot_mac = slot_for(b, per_inst ? "conv_inst_direct_kernel" : "conv_direct_kernel");
     b->steps.push_back(st);
-    plan_note(b, "convolver node %u: direct FIR taps=%llu cin=%d cout=%d terms=%d", id, (unsigned long long)len, cv.cin,
-              cv.cout, cv.n_terms);
+    plan_note(b, "convolver node %u: direct FIR taps=%llu cin=%d cout=%d terms=%d%s", id, (unsigned long long)len, cv.cin,
+              cv.cout, cv.n_terms, per_inst ? " per-instance impulse responses" : "");
     return 0;
   }
   std::vector<Cplx> tw(cv.n);
@@ -239,7 +258,7 @@ int plan_convolver(waa_batch* b, uint32_t id) {
   if ((e = dev_upload(b, &d_tw, tw))) return e;
   cv.tw = d_tw;
   Cplx *dH = nullptr, *dX = nullptr, *dY = nullptr;
-  if ((e = dev_alloc(b, &dH, (size_t)ir_nch * cv.parts * cv.n))) return e;
+  if ((e = dev_alloc(b, &dH, (size_t)(per_inst ? b->n_inst : 1) * ir_nch * cv.parts * cv.n))) return e;
   if ((e = dev_alloc(b, &dX, (size_t)cv.n_pairs * cv.cin * cv.nb * cv.n))) return e;
   if ((e = dev_alloc(b, &dY, (size_t)cv.n_pairs * cv.cout * cv.nb * cv.n))) return e;
   cv.H = dH;
@@ -260,13 +279,34 @@ int plan_convolver(waa_batch* b, uint32_t id) {
     launch_conv_ir_spectra(cv, b->stream);  // control-side work of ConvolverNode::set_buffer, once
     HIP_TRY(hipGetLastError());
   }
-  plan_note(b, "convolver node %u: fft B=%d N=%d P=%d blocks=%d pairs=%u cin=%d cout=%d terms=%d ir_len=%llu%s", id, cv.block,
+  plan_note(b, "convolver node %u: fft B=%d N=%d P=%d blocks=%d pairs=%u cin=%d cout=%d terms=%d ir_len=%llu%s%s", id, cv.block,
             cv.n, cv.parts, cv.nb, cv.n_pairs, cv.cin, cv.cout, cv.n_terms, (unsigned long long)len,
-            cv.pre_coefs ? " (+ the Biquad in front, in the forward transform)" : lti ? " (+ the Biquad in front, in the impulse response)" : "");
+            cv.pre_coefs ? " (+ the Biquad in front, in the forward transform)" : lti ? " (+ the Biquad in front, in the impulse response)" : "",
+            per_inst ? " per-instance impulse responses" : "");
   st.slot_fwd = slot_for(b, "conv_fft_kernel<fwd>");
-  st.slot_mac = slot_for(b, "conv_mac_kernel");
+  st.slot_mac = slot_for(b, per_inst ? "conv_inst_mac_kernel" : "conv_mac_kernel");
   st.slot_inv = slot_for(b, "conv_fft_kernel<inv>");
   b->steps.push_back(st);
+  if (per_inst) {
+    // An output channel all of whose terms use an all-zero response channel of THIS instance is exact zeros in the reference (an
+    // FFTConvolver without taps puts out zeros).  The product gives 0 * A for it, but the instance shares its inverse transform
+    // with its partner: what comes out is the partner's rounding noise (~1e-9), not zeros — cleared here, behind the inverse.
+    uint32_t cleared = 0;
+    for (uint32_t inst = 0; inst < b->n_inst; inst++)
+      for (int co = 0; co < cv.cout; co++) {
+        bool silent = true;
+        for (int t = 0; t < cv.n_terms; t++)
+          if (cv.terms[t].out_ch == co && conv_trimmed(n.ir_of(inst, cv.terms[t].ir_ch), n.ir_len) > 0) silent = false;
+        if (!silent) continue;
+        Step z;
+        z.kind = 3;
+        z.zero_ptr = n.sig.base + (uint64_t)inst * n.sig.inst_stride + (uint64_t)co * n.sig.ch_stride;
+        z.zero_bytes = (size_t)b->lp * sizeof(float);
+        b->steps.push_back(z);
+        cleared++;
+      }
+    if (cleared) plan_note(b, "convolver node %u: %u output channel(s) of instances with an all-zero response channel -> zero fill", id, cleared);
+  }
   return 0;
 }
 
