@@ -147,6 +147,8 @@ enum {
  *                 d[0] ref_distance, d[1] max_distance, d[2] rolloff_factor,
  *                 d[3] cone_inner_angle, d[4] cone_outer_angle, d[5] cone_outer_gain
  *     ANALYSER    i[0] = fft_size, d[0] smoothing_time_constant, d[1] min_decibels, d[2] max_decibels
+ *                 i[1] = series hop H in render quanta (0: one pull per render), i[2] = first pull quantum F >= 0: a whole
+ *                 series of pulls at q_k = F + k H <= n_quanta through the analyser getters (see there)
  *     WAVESHAPER  i[0] = oversample
  *     CONVOLVER   i[0] = disable_normalization (0/1)
  *                 i[1] = 0: one impulse response for the whole batch; 1: one impulse response per instance — every
@@ -480,7 +482,24 @@ waa_status waa_shard_range(uint32_t n_total, uint32_t part, uint32_t n_parts, ui
 waa_status waa_output_device(waa_batch* batch, const float** device_ptr, uint64_t* instance_stride,
                              uint64_t* channel_stride);
 
-/* ---- analyser (control-side pulls after the render; current_time = end of render) ------ */
+/* ---- analyser (control-side pulls after the render; current_time = end of render) ------
+ *
+ * A SERIES node (waa_node_desc.i[1] = H > 0, i[2] = F; spectrograms) answers the same eight getters with the rows of P pulls
+ * at the render quanta q_k = F + k H, every q_k <= n_quanta (a truncated last quantum counts).  The program of the reference
+ * it stands for, per context, on a fresh analyser:
+ *     for every q_k < n_quanta:  suspend_sync(q_k * 128 / sample_rate, |_| analyser.get_*_data(row_k))   (offline.rs:359-397)
+ *     start_rendering_sync();    if q_k == n_quanta: analyser.get_*_data(row_k)
+ * The pull at quantum q sees frames [q * 128 - fft_size, q * 128) of the mono down-mix of the node's input, zeros in front of
+ * frame 0 (a pull at q = 0: -inf dB, byte 0, samples 0); the smoothed spectrum carries from one pull to the next
+ * (value = tau * last + (1 - tau) * norm, a non-finite value becomes 0, analysis.rs:337-344).
+ * Layout: the *_batch getters write dst[n_instances][P][n], the per-instance getters dst[P][n]; row (i, k) receives what the
+ * reference's getter writes at pull k of context i: min(n, frequencyBinCount) resp. min(n, fftSize) values (the most recent
+ * ones), the rest of the row as the reference leaves it (untouched; the byte time-domain getter fills it with 128).
+ * A series is computed once per render and per kind on the device (the float and byte frequency kinds share one transform
+ * pass), buffers exist only for the kinds that were pulled, repeated calls return the same data, waa_batch_rearm and a new
+ * render drop it.  Before a render, for a node that does not reach the destination and for a plan-only batch the rows are
+ * those of an all-zero ring buffer, in the same layout.  H < 0, F < 0 and a series without a pull inside the render are
+ * WAA_ERR_INVALID_ARGUMENT at waa_batch_create. */
 waa_status waa_analyser_get_float_frequency_data(waa_batch* batch, uint32_t node, uint32_t instance, float* dst,
                                                  uint32_t n);
 waa_status waa_analyser_get_byte_frequency_data(waa_batch* batch, uint32_t node, uint32_t instance, uint8_t* dst,

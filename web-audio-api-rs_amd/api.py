@@ -950,10 +950,20 @@ class AnalyserNode(AudioNode):
     kind = NODE_ANALYSER
 
     def __init__(self, ctx, fft_size=2048, smoothing_time_constant=0.8, min_decibels=-100.0, max_decibels=-30.0,
-                 **kw):
+                 series_hop=0, series_first=0, **kw):
         super().__init__(ctx, **kw)
         self.fft_size, self.smoothing_time_constant = fft_size, smoothing_time_constant
         self.min_decibels, self.max_decibels = min_decibels, max_decibels
+        # a whole series of pulls (spectrograms): one every `series_hop` render quanta from quantum `series_first` on; 0 = off
+        self.series_hop, self.series_first = int(series_hop), int(series_first)
+
+    @property
+    def series_quanta(self) -> np.ndarray:
+        """The render quanta q_k = series_first + k * series_hop <= n_quanta at which the series pulls (empty: not a series node)."""
+        n_quanta = (self.context.length + RENDER_QUANTUM_SIZE - 1) // RENDER_QUANTUM_SIZE
+        if self.series_hop <= 0 or self.series_first < 0:
+            return np.zeros(0, np.int64)
+        return np.arange(self.series_first, n_quanta + 1, self.series_hop, dtype=np.int64)
 
     @property
     def frequency_bin_count(self) -> int:
@@ -962,8 +972,58 @@ class AnalyserNode(AudioNode):
     def _fill_desc(self, d):
         d.i[0] = self.fft_size
         d.d[0], d.d[1], d.d[2] = self.smoothing_time_constant, self.min_decibels, self.max_decibels
+        if self.series_hop != 0 and self.context._b.prefix != "waa_":
+            raise WaaError(4, "a series of analyser pulls is a feature of the device library; this binding pulls once per render")
+        # (the device library validates both fields; a prefix render serves ONE pull of a plain analyser at its own last quantum)
+        if self.context._b.prefix == "waa_" and not self.context._in_prefix:
+            d.i[1], d.i[2] = self.series_hop, self.series_first
+
+    def _not_series(self):
+        if self.series_hop != 0:
+            raise ValueError("this AnalyserNode pulls a series (series_hop > 0): use the get_*_data_series methods")
+
+    def _pull_series(self, fn_name: str, n: int, dtype, out=None):
+        """[n_instances][P][n]: every pull of the series of every context (computed once per render and kind on the device).
+
+        Pulls made inside a suspend_sync callback are not part of this: they still go through prefix renders and still start
+        from a zero spectrum each."""
+        ctx = self.context
+        if self.series_hop <= 0:
+            raise ValueError("this AnalyserNode pulls once per render (series_hop = 0): use the get_*_data / get_*_data_all methods")
+        if ctx._handle is None or ctx._now_q > 0:
+            raise WaaError(3, "InvalidStateError - analyser data is only available after start_rendering_sync")
+        shape = (ctx.n_instances, len(self.series_quanta), n)
+        if out is None:
+            out = np.zeros(shape, dtype=dtype)
+        if not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != dtype or not out.flags.c_contiguous:
+            # (the library writes n values per pull and context through the raw pointer: a wrong buffer is a silent out-of-bounds write)
+            raise ValueError(f"out: expected a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+        ptr = out.ctypes.data_as(_FP if dtype == np.float32 else C.POINTER(C.c_uint8))
+        ctx._b.check(getattr(ctx._b, fn_name)(ctx._handle, self.id, ptr, n))
+        return out
+
+    def get_float_frequency_data_series(self, n: Optional[int] = None, out=None) -> np.ndarray:
+        """[n_instances][P][n] dB rows of the series, the smoothed spectrum carried from pull to pull as the reference carries it.
+        Pulls made inside a suspend_sync callback still go through prefix renders and still start from a zero spectrum each."""
+        return self._pull_series("analyser_get_float_frequency_data_batch", n or self.frequency_bin_count, np.float32, out)
+
+    def get_byte_frequency_data_series(self, n: Optional[int] = None, out=None) -> np.ndarray:
+        """[n_instances][P][n] byte rows of the series (same transform pass as the float rows).
+        Pulls made inside a suspend_sync callback still go through prefix renders and still start from a zero spectrum each."""
+        return self._pull_series("analyser_get_byte_frequency_data_batch", n or self.frequency_bin_count, np.uint8, out)
+
+    def get_float_time_domain_data_series(self, n: Optional[int] = None, out=None) -> np.ndarray:
+        """[n_instances][P][n]: the most recent n frames of the mono down-mix in front of every pull.
+        Pulls made inside a suspend_sync callback still go through prefix renders."""
+        return self._pull_series("analyser_get_float_time_domain_data_batch", n or self.fft_size, np.float32, out)
+
+    def get_byte_time_domain_data_series(self, n: Optional[int] = None, out=None) -> np.ndarray:
+        """[n_instances][P][n]: the byte form of the time-domain rows (128 behind fft_size values, as the reference writes).
+        Pulls made inside a suspend_sync callback still go through prefix renders."""
+        return self._pull_series("analyser_get_byte_time_domain_data_batch", n or self.fft_size, np.uint8, out)
 
     def _pull(self, fn_name: str, n: int, instance: int, dtype):
+        self._not_series()
         ctx = self.context
         if ctx._now_q > 0 and ctx._handle is None:  # inside a suspend_sync callback: what has been rendered up to here
             with ctx._prefix_render(ctx._now_q):
@@ -977,6 +1037,7 @@ class AnalyserNode(AudioNode):
 
     def _pull_all(self, fn_name: str, n: int, dtype, out=None):
         """[n_instances][n]: every context's pull in one call (one launch, one transfer on the device)."""
+        self._not_series()
         ctx = self.context
         if ctx._now_q > 0 and ctx._handle is None:
             with ctx._prefix_render(ctx._now_q):
@@ -1246,6 +1307,7 @@ class OfflineAudioContext:
         self._suspends = {}
         self._ctl = {}
         self._now_q = 0
+        self._in_prefix = False  # inside _prefix_render: series analysers are described as plain ones
         self._replayed = 0  # the control log has been replayed up to this quantum on the current batch
         self._live = []   # the connections that exist "now" (disconnect's InvalidAccessError, disconnect() of everything)
         self._state = "suspended"  # AudioContextState of a context that has not started rendering (offline.rs:451)
@@ -1397,6 +1459,7 @@ class OfflineAudioContext:
         def scope():
             now, replayed, rendered = self._now_q, self._replayed, self._rendered
             self._now_q = 0
+            self._in_prefix = True
             try:
                 self._build(length=q * RENDER_QUANTUM_SIZE, run_callbacks=False)
                 self._replayed = 0
@@ -1406,6 +1469,7 @@ class OfflineAudioContext:
                 if self._handle is not None:
                     self._b.batch_destroy(self._handle)
                 self._handle = None
+                self._in_prefix = False
                 self._now_q, self._replayed, self._rendered = now, replayed, rendered
         return scope()
 

@@ -188,6 +188,13 @@ waa_status waa_batch_create(const waa_graph_desc* g, uint32_t n_inst, uint32_t n
         if (n.desc.d[0] < 0. || n.desc.d[0] > 1.)
           return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - Invalid smoothing time constant");
         if (!(n.desc.d[1] < n.desc.d[2])) return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - Invalid min decibels");
+        // a series of pulls: i[1] = hop in quanta (0: one pull per render), i[2] = first pull quantum
+        if (n.desc.i[1] < 0 || n.desc.i[2] < 0)
+          return fail(WAA_ERR_INVALID_ARGUMENT, "AnalyserNode %u: series hop i[1] = %d and first pull quantum i[2] = %d cannot be negative", i,
+                      n.desc.i[1], n.desc.i[2]);
+        if (n.desc.i[1] > 0 && n.an_series_pulls(b->n_quanta) == 0)
+          return fail(WAA_ERR_INVALID_ARGUMENT, "AnalyserNode %u: no pull of the series falls inside the render (first pull at quantum %d, the render has %u)",
+                      i, n.desc.i[2], b->n_quanta);
         break;
       }
       case WAA_NODE_CHANNEL_SPLITTER: {  // ChannelSplitterNode::new, channel_splitter.rs:146-161
@@ -1272,6 +1279,14 @@ static int timed_build_plan(waa_batch* b) {
   if (!e) e = build_plan(b);
   if (!e && !b->prepass_note.empty()) b->plan_log.push_back(b->prepass_note);
   if (!e && !b->timed_note.empty()) b->plan_log.push_back(b->timed_note);
+  for (uint32_t i = 0; !e && i < b->n_user_nodes; i++) {
+    const Node& n = b->nodes[i];
+    if (!n.an_series()) continue;
+    char note[200];
+    snprintf(note, sizeof note, "analyser series: node %u, %u pull(s) every %d quanta from quantum %d, fft_size %d", i,
+             n.an_series_pulls(b->n_quanta), n.desc.i[1], n.desc.i[2], n.desc.i[0]);
+    b->plan_log.push_back(note);
+  }
   b->t_plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   b->plan_alloc_ms = b->t_alloc_ms - a0;
   b->plan_upload_ms = b->t_upload_ms - u0;
@@ -1806,7 +1821,27 @@ waa_status waa_output_device(waa_batch* b, const float** p, uint64_t* is, uint64
 // AnalyserNode pulls (analysis.rs:261-401).  current_time after an offline render never changes, so the spectra of ALL
 // instances are computed once per render — one launch, one workgroup per context — and every pull, per instance or for
 // the whole batch, is a view into that result (repeated pulls return the same data, analysis.rs:354-357).
-enum { AN_DB = 0, AN_BYTES = 1, AN_TIME = 2 };
+enum { AN_DB = 0, AN_BYTES = 1, AN_TIME = 2, AN_TBYTES = 3 };
+// the Blackman window and the twiddles of the packed real transform, uploaded on first use
+static int analyser_tables(waa_batch* b, Node& n) {
+  if (n.d_window) return 0;
+  const int N = n.desc.i[0], M = N / 2;
+  int e;
+  // generate_blackman (analysis.rs:14-24), f32 with the host libm the reference's f32::cos resolves to
+  std::vector<float> win(N);
+  const float alpha = 0.16f, a0 = (1.f - alpha) / 2.f, a1 = 1.f / 2.f, a2 = alpha / 2.f;
+  for (int i = 0; i < N; i++)
+    win[i] = a0 - a1 * cosf(2.f * PI_F * (float)i / (float)N) + a2 * cosf(4.f * PI_F * (float)i / (float)N);
+  std::vector<Cplx> tw(M), twf(M);
+  for (int t = 0; t < M; t++) {
+    const double x = -2.0 * 3.14159265358979323846 * (double)t / (double)M;
+    const double y = -2.0 * 3.14159265358979323846 * (double)t / (double)N;
+    tw[t] = Cplx{(float)std::cos(x), (float)std::sin(x)};
+    twf[t] = Cplx{(float)std::cos(y), (float)std::sin(y)};
+  }
+  if ((e = dev_upload(b, &n.d_window, win)) || (e = dev_upload(b, &n.d_an_tw, tw)) || (e = dev_upload(b, &n.d_an_twfull, twf))) return e;
+  return 0;
+}
 static int analyser_compute(waa_batch* b, uint32_t node, int what) {
   int e;
   if ((e = check_node(b, node, WAA_NODE_ANALYSER))) return e;
@@ -1828,23 +1863,10 @@ static int analyser_compute(waa_batch* b, uint32_t node, int what) {
   }
   HIP_TRY(hipSetDevice(b->device));
   if (!n.an.computed) {
-    if (!n.d_window) {
-      // generate_blackman (analysis.rs:14-24), f32 with the host libm the reference's f32::cos resolves to
-      std::vector<float> win(N);
-      const float alpha = 0.16f, a0 = (1.f - alpha) / 2.f, a1 = 1.f / 2.f, a2 = alpha / 2.f;
-      for (int i = 0; i < N; i++)
-        win[i] = a0 - a1 * cosf(2.f * PI_F * (float)i / (float)N) + a2 * cosf(4.f * PI_F * (float)i / (float)N);
-      std::vector<Cplx> tw(M), twf(M);
-      for (int t = 0; t < M; t++) {
-        const double x = -2.0 * 3.14159265358979323846 * (double)t / (double)M;
-        const double y = -2.0 * 3.14159265358979323846 * (double)t / (double)N;
-        tw[t] = Cplx{(float)std::cos(x), (float)std::sin(x)};
-        twf[t] = Cplx{(float)std::cos(y), (float)std::sin(y)};
-      }
+    if ((e = analyser_tables(b, n))) return e;
+    if (!n.d_an_db) {
       std::vector<float> zeros(M, 0.f);
-      if ((e = dev_upload(b, &n.d_window, win)) || (e = dev_upload(b, &n.d_an_tw, tw)) ||
-          (e = dev_upload(b, &n.d_an_twfull, twf)) || (e = dev_upload(b, &n.d_an_prev, zeros)) ||
-          (e = dev_alloc(b, &n.d_an_db, ni * M)) || (e = dev_alloc(b, &n.d_an_bytes, ni * M)) ||
+      if ((e = dev_upload(b, &n.d_an_prev, zeros)) || (e = dev_alloc(b, &n.d_an_db, ni * M)) || (e = dev_alloc(b, &n.d_an_bytes, ni * M)) ||
           (e = dev_alloc(b, &n.d_an_time, ni * N)))
         return e;
     }
@@ -1900,10 +1922,122 @@ static int analyser_compute(waa_batch* b, uint32_t node, int what) {
   }
   return 0;
 }
+
+// A series node (desc.i[1] > 0, include/waa_hip.h): the rows of ALL pulls of ALL instances, computed once per render and per kind
+// on the device (waa_analyser_series.hip) and kept there; a getter call copies its rows [i0, i1) x [P] out, `nn` elements apart.
+static int analyser_series_rows(waa_batch* b, uint32_t node, int what, uint32_t i0, uint32_t i1, void* dst, uint32_t nn) {
+  Node& n = b->nodes[node];
+  const uint32_t N = (uint32_t)n.desc.i[0], M = N / 2, P = n.an_series_pulls(b->n_quanta);
+  const size_t ni = b->n_inst;
+  const bool freq = what == AN_DB || what == AN_BYTES, bytes = what == AN_BYTES || what == AN_TBYTES;
+  const uint32_t W = freq ? M : N, len = std::min(nn, W);
+  const size_t es = bytes ? 1 : sizeof(float), rows = (size_t)(i1 - i0) * P;
+  const bool on_device = b->planned && b->rendered && n.live && !b->dry;
+  if (on_device)
+    if (int es2 = waa_settle_loops(b)) return es2;  // (run_steps resets the analysers' caches: the pulls below see the settled render)
+  if (what == AN_TBYTES && nn > len)  // analysis.rs:268-276: elements past fft_size come from a zeroed tmp
+    for (size_t r = 0; r < rows; r++) std::memset((uint8_t*)dst + r * nn + len, 128, nn - len);
+  if (!on_device) {
+    // nothing rendered (or the node does not reach the destination): every pull sees an all-zero ring buffer
+    for (size_t r = 0; r < rows; r++) {
+      if (what == AN_DB)
+        std::fill_n((float*)dst + r * nn, len, -INFINITY);  // 20 log10(0)
+      else if (what == AN_BYTES)
+        std::memset((uint8_t*)dst + r * nn, 0, len);         // (-inf - min) scaled and clamped
+      else if (what == AN_TIME)
+        std::fill_n((float*)dst + r * nn, len, 0.f);
+      else
+        std::memset((uint8_t*)dst + r * nn, 128, len);
+    }
+    return WAA_OK;
+  }
+  HIP_TRY(hipSetDevice(b->device));
+  int e;
+  if ((e = analyser_tables(b, n))) return e;
+  AnalyserSeriesDesc sd{};
+  sd.a.sig = n.sig;
+  sd.a.n_inst = b->n_inst;
+  sd.a.fft_size = (int32_t)N;
+  sd.a.smoothing = (float)n.desc.d[0];
+  sd.a.min_db = (float)n.desc.d[1];
+  sd.a.max_db = (float)n.desc.d[2];
+  sd.a.window = n.d_window;
+  sd.a.tw = n.d_an_tw;
+  sd.a.tw_full = n.d_an_twfull;
+  sd.a.code = b->dynamic ? n.code : nullptr;
+  sd.a.code_stride = b->code_stride;
+  sd.hop = n.desc.i[1];
+  sd.first = n.desc.i[2];
+  sd.pulls = (int32_t)P;
+  sd.frames = (uint64_t)b->n_quanta * RQ;
+  analyser_series_shape(&sd);
+  auto timed = [&](const char* name, auto&& launch) -> int {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const int slot = b->profiling ? slot_for(b, name) : -1;
+    if (slot >= 0) {
+      HIP_TRY(hipEventCreate(&e0));
+      HIP_TRY(hipEventCreate(&e1));
+      HIP_TRY(hipEventRecord(e0, b->stream));
+    }
+    launch();
+    HIP_TRY(hipGetLastError());
+    if (slot >= 0) {
+      HIP_TRY(hipEventRecord(e1, b->stream));
+      b->prof[slot].pending.push_back({e0, e1});
+    }
+    return 0;
+  };
+  const size_t nf = ni * P * M, nt = ni * P * N;
+  const void* src = nullptr;
+  if (freq) {
+    const bool smooth = sd.a.smoothing > 0.f;
+    if (what == AN_BYTES && !n.d_ans_bytes && (e = dev_alloc(b, &n.d_ans_bytes, nf))) return e;
+    // dB rows: asked for, the recursion's workspace (the unsmoothed magnitudes in f32), or there from an earlier render and not
+    // current — the pass that is about to run fills them too, so that float rows asked for later do not transform again
+    const bool need_db = what == AN_DB || (smooth && !n.an.s_bytes) || (n.d_ans_db && !n.an.s_db);
+    if (need_db && !n.d_ans_db && (e = dev_alloc(b, &n.d_ans_db, nf))) return e;
+    sd.db_out = n.d_ans_db;
+    sd.byte_out = n.d_ans_bytes;
+    if (what == AN_BYTES && !n.an.s_bytes && n.an.s_db) {
+      if ((e = timed("analyser_series_bytes_kernel", [&] { launch_analyser_series_bytes(sd, b->stream); }))) return e;
+      n.an.s_bytes = true;
+    } else if (!(what == AN_DB ? n.an.s_db : n.an.s_bytes)) {
+      // one transform pass for every frequency kind that has a buffer by now and is not current
+      if (!need_db) sd.db_out = nullptr;
+      if (n.an.s_bytes) sd.byte_out = nullptr;
+      sd.lin = smooth ? 1 : 0;
+      if ((e = timed("analyser_series_fft_kernel", [&] { launch_analyser_series_fft(sd, b->stream); }))) return e;
+      if (smooth && (e = timed("analyser_series_smooth_kernel", [&] { launch_analyser_series_smooth(sd, b->stream); }))) return e;
+      n.an.s_db |= sd.db_out != nullptr;
+      n.an.s_bytes |= sd.byte_out != nullptr;
+    }
+    src = what == AN_DB ? (const void*)n.d_ans_db : (const void*)n.d_ans_bytes;
+  } else {
+    if (what == AN_TIME && !n.d_ans_time && (e = dev_alloc(b, &n.d_ans_time, nt))) return e;
+    if (what == AN_TBYTES && !n.d_ans_tbytes && (e = dev_alloc(b, &n.d_ans_tbytes, nt))) return e;
+    if (!(what == AN_TIME ? n.an.s_time : n.an.s_tbytes)) {
+      // (both forms in one gather when both have a buffer and neither is current)
+      sd.time_out = n.an.s_time ? nullptr : n.d_ans_time;
+      sd.tbyte_out = n.an.s_tbytes ? nullptr : n.d_ans_tbytes;
+      if ((e = timed("analyser_series_time_kernel", [&] { launch_analyser_series_time(sd, b->stream); }))) return e;
+      n.an.s_time |= sd.time_out != nullptr;
+      n.an.s_tbytes |= sd.tbyte_out != nullptr;
+    }
+    src = what == AN_TIME ? (const void*)n.d_ans_time : (const void*)n.d_ans_tbytes;
+  }
+  // ring_buffer.read hands out the most recent `len` frames (analysis.rs:114-127); frequency rows start at bin 0
+  const char* from = (const char*)src + ((size_t)i0 * P * W + (freq ? 0 : W - len)) * es;
+  // (pageable caller memory goes through the batch's pinned staging block: the device only touches memory this library pinned)
+  if ((e = waa_internal_xfer_d2h(b, dst, (size_t)nn * es, from, (size_t)W * es, (size_t)len * es, rows))) return e;
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return WAA_OK;
+}
 // rows [i0, i1) of one result kind -> dst rows of `nn` elements
 static int analyser_rows(waa_batch* b, uint32_t node, int what, uint32_t i0, uint32_t i1, void* dst, uint32_t nn) {
-  int e = analyser_compute(b, node, what);
+  int e = check_node(b, node, WAA_NODE_ANALYSER);
   if (e) return e;
+  if (b->nodes[node].an_series()) return analyser_series_rows(b, node, what, i0, i1, dst, nn);
+  if ((e = analyser_compute(b, node, what))) return e;
   const Node& n = b->nodes[node];
   const uint32_t N = (uint32_t)n.desc.i[0], M = N / 2;
   for (uint32_t i = i0; i < i1; i++) {
@@ -1921,8 +2055,10 @@ static int analyser_rows(waa_batch* b, uint32_t node, int what, uint32_t i0, uin
   return WAA_OK;
 }
 static int analyser_byte_time_rows(waa_batch* b, uint32_t node, uint32_t i0, uint32_t i1, uint8_t* dst, uint32_t nn) {
-  int e = analyser_compute(b, node, AN_TIME);
+  int e = check_node(b, node, WAA_NODE_ANALYSER);
   if (e) return e;
+  if (b->nodes[node].an_series()) return analyser_series_rows(b, node, AN_TBYTES, i0, i1, dst, nn);
+  if ((e = analyser_compute(b, node, AN_TIME))) return e;
   const Node& n = b->nodes[node];
   const uint32_t N = (uint32_t)n.desc.i[0];
   const uint32_t len = std::min(nn, N);

@@ -21,53 +21,13 @@
 
 #include <cstdlib>
 
+#include "waa_analyser_common.hpp"
 #include "waa_internal.hpp"
 
 namespace waa {
 
 namespace {
 
-__device__ __forceinline__ Cplx cmul(Cplx a, Cplx b) {
-  Cplx r;
-  r.re = __builtin_fmaf(a.re, b.re, -(a.im * b.im));
-  r.im = __builtin_fmaf(a.re, b.im, a.im * b.re);
-  return r;
-}
-__device__ __forceinline__ Cplx cadd(Cplx a, Cplx b) { return Cplx{a.re + b.re, a.im + b.im}; }
-__device__ __forceinline__ Cplx csub(Cplx a, Cplx b) { return Cplx{a.re - b.re, a.im - b.im}; }
-__device__ __forceinline__ Cplx mul_negi(Cplx a) { return Cplx{a.im, -a.re}; }  // a * (-i)
-__device__ __forceinline__ Cplx mul_posi(Cplx a) { return Cplx{-a.im, a.re}; }  // a * (+i)
-__device__ __forceinline__ Cplx conj(Cplx a) { return Cplx{a.re, -a.im}; }
-
-// in-place radix-4 decimation-in-frequency FFT: natural order in, bit-reversed order out. n = 4^m.
-// n = 4^m or 2 * 4^m (a trailing radix-2 stage on adjacent pairs)
-__device__ __forceinline__ void fft_dif(Cplx* a, const Cplx* tw, int n, int tid, int nthreads) {
-  int L = n;
-  for (; L >= 4; L >>= 2) {
-    const int q = L >> 2;
-    const int tstep = n / (4 * q);
-    for (int b = tid; b < (n >> 2); b += nthreads) {
-      const int j = b % q, base = (b / q) * 4 * q + j;
-      const Cplx x0 = a[base], x1 = a[base + q], x2 = a[base + 2 * q], x3 = a[base + 3 * q];
-      const Cplx s02 = cadd(x0, x2), d02 = csub(x0, x2), s13 = cadd(x1, x3), d13 = mul_negi(csub(x1, x3));
-      const Cplx w1 = tw[j * tstep];
-      const Cplx w2 = cmul(w1, w1), w3 = cmul(w2, w1);
-      a[base] = cadd(s02, s13);
-      a[base + q] = cmul(csub(s02, s13), w2);
-      a[base + 2 * q] = cmul(cadd(d02, d13), w1);
-      a[base + 3 * q] = cmul(csub(d02, d13), w3);
-    }
-    __syncthreads();
-  }
-  if (L == 2) {
-    for (int b = tid; b < (n >> 1); b += nthreads) {
-      const Cplx u = a[2 * b], v = a[2 * b + 1];
-      a[2 * b] = cadd(u, v);
-      a[2 * b + 1] = csub(u, v);
-    }
-    __syncthreads();
-  }
-}
 // in-place radix-4 decimation-in-time inverse FFT: bit-reversed order in, natural order out (unscaled).
 __device__ __forceinline__ void fft_dit_inv(Cplx* a, const Cplx* tw, int n, int tid, int nthreads) {
   int q0 = 1;
@@ -858,32 +818,11 @@ __global__ void analyser_kernel(const AnalyserDesc d) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const int N = d.fft_size, M = N >> 1;
   const uint32_t inst = blockIdx.x;
-  const float* p0 = d.sig.base + (uint64_t)inst * d.sig.inst_stride;
   float* time_out = d.time_out + (uint64_t)inst * N;
   const int64_t first = (int64_t)d.frames_written - N;  // ring_buffer.read: the last N frames written
   for (int i = tid; i < N; i += nt) {
     const int64_t f = first + i;
-    float v = 0.f;
-    if (f >= 0) {
-      // mono down-mix of the analyser input (analyser.rs:277-280, quantum.rs:387-397)
-      const uint64_t cs = d.sig.ch_stride;
-      int nch = d.sig.nch;
-      if (d.code) {  // (dynamic-count plans: the count of this frame's quantum)
-        const uint32_t c = d.code[(uint64_t)inst * d.code_stride + (uint64_t)(f >> 7)];
-        nch = (c & 0x80u) ? 0 : (int)(c & 63u);
-      }
-      switch (nch) {  // quantum.rs:387-429 speaker down-mix to mono
-        case 0: v = 0.f; break;  // (a silent quantum)
-        case 1: v = p0[f]; break;
-        case 2: v = 0.5f * (p0[f] + p0[cs + f]); break;
-        case 4: v = 0.25f * (p0[f] + p0[cs + f] + p0[2 * cs + f] + p0[3 * cs + f]); break;
-        case 6:
-          v = __builtin_fmaf(0.70710678118654752440f, p0[f] + p0[cs + f],
-                             __builtin_fmaf(0.5f, p0[4 * cs + f] + p0[5 * cs + f], p0[2 * cs + f]));
-          break;
-        default: v = p0[f]; break;  // other layouts: truncate
-      }
-    }
+    const float v = f >= 0 ? analyser_mono(d.sig, d.code, d.code_stride, inst, f) : 0.f;
     time_out[i] = v;
     const float wv = v * d.window[i];
     reinterpret_cast<float*>(a)[i] = wv;  // z[n] = x[2n] + i x[2n+1]
@@ -895,22 +834,12 @@ __global__ void analyser_kernel(const AnalyserDesc d) {
   const float tau = d.smoothing;
   const float bscale = 255.f / (d.max_db - d.min_db);
   for (int k = tid; k < M; k += nt) {
-    const int k2 = (M - k) & (M - 1);
-    const Cplx z = a[__brev((unsigned)k) >> (32 - lg)];
-    const Cplx zc = conj(a[__brev((unsigned)k2) >> (32 - lg)]);
-    const Cplx e = Cplx{0.5f * (z.re + zc.re), 0.5f * (z.im + zc.im)};
-    const Cplx o = mul_negi(Cplx{0.5f * (z.re - zc.re), 0.5f * (z.im - zc.im)});
-    const Cplx w = d.tw_full[k];  // exp(-2 pi i k / N)
-    const Cplx x = cadd(e, cmul(o, w));
-    const float norm = hypotf(x.re, x.im) * nf;
+    const float norm = analyser_bin_norm(a, d.tw_full, k, M, lg, nf);
     float value = tau * d.prev[k] + (1.f - tau) * norm;
     value = isfinite(value) ? value : 0.f;
     const float db = 20.f * log10f(value);  // analysis.rs:365-368
     d.db_out[(uint64_t)inst * M + k] = db;
-    // analysis.rs:388-400
-    const float scaled = bscale * (db - d.min_db);
-    const float clamped = scaled < 0.f ? 0.f : scaled > 255.f ? 255.f : scaled;
-    d.byte_out[(uint64_t)inst * M + k] = isnan(scaled) ? (uint8_t)0 : (uint8_t)clamped;
+    d.byte_out[(uint64_t)inst * M + k] = analyser_byte(db, d.min_db, bscale);
   }
 }
 

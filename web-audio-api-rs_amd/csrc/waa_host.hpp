@@ -180,7 +180,18 @@ struct Node {
     bool have_db = false, have_bytes = false, have_time = false;  // ... and downloaded
     std::vector<float> db, time;        // [n_inst][fft_size / 2], [n_inst][fft_size]
     std::vector<uint8_t> bytes;         // [n_inst][fft_size / 2]
+    // a series node (desc.i[1] > 0): which kinds of the series the device buffers below hold for the current render (the rows
+    // stay on the device — a series is as large as the render's output — and every getter call copies from there)
+    bool s_db = false, s_bytes = false, s_time = false, s_tbytes = false;
   } an;
+  // series buffers, allocated when a kind is first pulled: [n_inst][P][fft_size / 2] dB and bytes, [n_inst][P][fft_size] time domain
+  float *d_ans_db = nullptr, *d_ans_time = nullptr;
+  uint8_t *d_ans_bytes = nullptr, *d_ans_tbytes = nullptr;
+  bool an_series() const { return desc.kind == WAA_NODE_ANALYSER && desc.i[1] > 0; }
+  // pulls at q_k = i[2] + k * i[1] <= n_quanta
+  uint32_t an_series_pulls(uint32_t n_quanta) const {
+    return an_series() && desc.i[2] >= 0 && (uint32_t)desc.i[2] <= n_quanta ? (n_quanta - (uint32_t)desc.i[2]) / (uint32_t)desc.i[1] + 1 : 0;
+  }
   float* d_window = nullptr;
   Cplx *d_an_tw = nullptr, *d_an_twfull = nullptr;
   float *d_an_prev = nullptr, *d_an_db = nullptr, *d_an_time = nullptr;

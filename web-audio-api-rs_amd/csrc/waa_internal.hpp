@@ -353,6 +353,27 @@ struct AnalyserDesc {
   uint64_t code_stride;
 };
 void launch_analyser(const AnalyserDesc& d, void* stream);
+// A series of pulls of one AnalyserNode (waa_node_desc.i[1] = hop > 0; waa_analyser_series.hip): pull k of every instance sees
+// frames [q_k * 128 - fft_size, q_k * 128) with q_k = first + k * hop, the smoothed spectrum carried from pull to pull.
+struct AnalyserSeriesDesc {
+  AnalyserDesc a;        // sig, n_inst, fft_size, smoothing, min_db, max_db, window, tw, tw_full, code, code_stride (the rest unused)
+  int32_t first, hop;    // F, H in render quanta
+  int32_t pulls;         // P
+  int32_t run;           // transform stage: consecutive pulls of one instance per workgroup
+  int32_t stage_span;    // ... which reads their span of the signal once, into LDS (run > 1)
+  int32_t lin;           // transform stage writes |X| / N into db_out: the recursion over the pulls follows (smoothing > 0)
+  uint64_t frames;       // frames of `sig` that may be read: n_quanta * 128
+  float* db_out;         // [n_inst][P][fft_size / 2] (null: bytes only)
+  uint8_t* byte_out;     // [n_inst][P][fft_size / 2] (null: not asked for)
+  float* time_out;       // [n_inst][P][fft_size] (null: not asked for)
+  uint8_t* tbyte_out;    // [n_inst][P][fft_size] (null: not asked for)
+};
+// run length and LDS layout of the transform stage for this shape (fills run / stage_span)
+void analyser_series_shape(AnalyserSeriesDesc* d);
+void launch_analyser_series_fft(const AnalyserSeriesDesc& d, void* stream);     // transforms of all (instance, pull)
+void launch_analyser_series_smooth(const AnalyserSeriesDesc& d, void* stream);  // recursion over the pulls, in place, + dB / bytes
+void launch_analyser_series_bytes(const AnalyserSeriesDesc& d, void* stream);   // bytes from finished dB rows
+void launch_analyser_series_time(const AnalyserSeriesDesc& d, void* stream);    // time-domain rows (no transform)
 constexpr int DIRECT_MAX_TAPS = 128;  // trimmed IRs up to this length use the direct FIR kernel
 void launch_conv_direct(const ConvDesc& d, void* stream);
 void launch_conv_ir_spectra(const ConvDesc& d, void* stream);
