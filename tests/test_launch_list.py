@@ -1,0 +1,516 @@
+"""The launch list the planner hands to the executor, step by step, for a corpus of graphs that reaches every StepKind and
+every loop form: kind, loop group, quantum-block group, prologue flag, the echo fusions' marks, profile slots, the groups'
+block sizes (WAA_PLAN_LAUNCHES=1, measurement build) behind the plan's own text.  The expected texts under
+tests/golden/launch_lists/ were written by the planner as it was before its kinds had names (Step::kind a bare int) with the
+same dump patched in, so any refactor of the planner's kind handling has to reproduce them to the byte.  Plan-only batches, no
+GPU — except the one kind a plan-only batch cannot reach (Timeline: automation is replayed on the device only when there is
+one), whose graph is planned on the GPU."""
+import hashlib
+import os
+import re
+
+import numpy as np
+import pytest
+
+import web_audio_api_rs_amd as waa
+from graphs import c2, c4, c5, garage_like_ir, t1, white_noise
+from test_fuzz_graphs import build_random_graph
+
+pytestmark = pytest.mark.measure
+RQ, SR = 128, 48000.0
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_lists")
+# waa_host.hpp, enum StepKind
+KIND_NAMES = ["chain", "biquad_stream", "conv_fft", "zero_fill", "conv_direct", "biquad_coefs", "iir_stream", "delay", "loop", "osc",
+              "dyn", "conv_codes", "biquad_hp", "panner_geom", "timeline", "link", "qgemm", "hrtf", "biquad_tile_digest",
+              "biquad_lanes", "os_fft", "compressor", "route"]
+CURVE = np.tanh(np.linspace(-2.5, 2.5, 129)).astype(np.float32)
+
+
+def _ctx(be, n=3, frames=2048 * 8, n_out=2, device=waa.PLAN_ONLY):
+    return waa.OfflineAudioContext(n_out, frames, SR, n_instances=n, binding=be, device=device)
+
+
+def _source(c, n_ch=2, frames=None, seed0=0xA0D10, scale=1.0):
+    s = c.create_buffer_source()
+    s.set_buffer_batch(white_noise(c.n_instances, n_ch, frames or c.length, seed0=seed0) * np.float32(scale), SR)
+    s.start()
+    return s
+
+
+def _decaying_ir(n_ch, taps, seed):
+    rng = np.random.default_rng(seed)
+    return (rng.uniform(-1, 1, (n_ch, taps)) * np.exp(-np.arange(taps) / (0.3 * taps))[None, :]).astype(np.float32)
+
+
+# ---- the graphs (each builder: binding -> context) ----------------------------------------------------------------------
+def g_c2(be):
+    return c2(be, white_noise(3, 2, 480000), device=waa.PLAN_ONLY)[0]
+
+
+def g_t1(be):
+    return t1(be, white_noise(5, 2, 480000), garage_like_ir(), device=waa.PLAN_ONLY)[0]
+
+
+def g_c4(be):
+    return c4(be, white_noise(5, 2, 480000), garage_like_ir(), device=waa.PLAN_ONLY)[0]
+
+
+def g_c5(be):
+    ctx = c5(be, white_noise(2, 2, 5000), length=RQ * 50)[0]
+    ctx.device = waa.PLAN_ONLY
+    return ctx
+
+
+def _echo_loop(be, delay_time, shaper=False):
+    """source -> Delay <-> [WaveShaper ->] Gain, the delay into the destination"""
+    c = _ctx(be)
+    s = _source(c)
+    d = c.create_delay(1.0, delay_time=delay_time)
+    s.connect(d)
+    head = d.connect(c.create_wave_shaper(curve=np.float32([-1.0, 0.0, 1.0]))) if shaper else d
+    head.connect(c.create_gain(gain=0.5)).connect(d)
+    d.connect(c.destination())
+    return c
+
+
+def g_echo_ring(be):            # block-scheduled (2400 frames > a tile), one launch of the LDS-ring kernel
+    return _echo_loop(be, 0.05)
+
+
+def g_echo_ring_tail(be):       # ... whose line has one reader, dry + wet: the fused tail
+    c = _ctx(be)
+    s = _source(c)
+    d = c.create_delay(1.0, delay_time=0.05)
+    s.connect(d)
+    d.connect(c.create_gain(gain=0.5)).connect(d)
+    d.connect(c.destination())
+    s.connect(c.destination())
+    return c
+
+
+def g_loop_kernel(be):          # 132 frames: below the ring kernel's smallest chunk
+    return _echo_loop(be, 0.00275)
+
+
+def g_loop_kernel_shaper(be):   # 480 frames around a WaveShaper: planned for the ring, does not qualify, planned again
+    return _echo_loop(be, 0.01, shaper=True)
+
+
+def g_two_block_loops(be):      # two block-scheduled loops in a row: an echo on the ring kernel, then one around a WaveShaper
+    c = _ctx(be)
+    s = _source(c)
+    d1, d2 = c.create_delay(1.0, delay_time=0.05), c.create_delay(1.0, delay_time=0.06)
+    s.connect(d1)
+    d1.connect(c.create_gain(gain=0.5)).connect(d1)
+    d1.connect(d2)
+    d2.connect(c.create_wave_shaper(curve=np.float32([-1.0, 0.0, 1.0]))).connect(c.create_gain(gain=0.4)).connect(d2)
+    d2.connect(c.destination())
+    return c
+
+
+def g_block_loop_automated(be):
+    """a block-scheduled loop whose Biquad is a-rate automated and whose gain is modulated from outside the loop: coefficient
+    tables, digests and the param's summing chain run once in front of the blocks"""
+    c = _ctx(be)
+    s = _source(c)
+    d = c.create_delay(1.0, delay_time=0.05)
+    bq = c.create_biquad_filter(type_="bandpass", frequency=800.0, q=1.5)
+    bq.frequency.set_value_at_time(300.0, 0.0).exponential_ramp_to_value_at_time(4000.0, 0.3)
+    g = c.create_gain(gain=0.35)
+    lfo = c.create_oscillator(type_="sine", frequency=7.0)
+    lfo.connect(c.create_gain(gain=0.1)).connect(g.gain)
+    lfo.start()
+    s.connect(d)
+    d.connect(bq).connect(g).connect(d)
+    bq.connect(c.destination())
+    return c
+
+
+def g_filtered_echo_tail(be):
+    """source -> Delay -> Biquad -> Gain -> back, filter + source into the destination (tests/test_cycles.py): the ring kernel's
+    BQ form with the tail fused"""
+    n, frames = 6, 2048 * 11 + 77
+    c = _ctx(be, n=n, frames=frames)
+    s = _source(c, seed0=37)
+    delay, bq, fb = c.create_delay(0.4), c.create_biquad_filter(type_="lowpass", frequency=2500.0), c.create_gain()
+    delays = (np.float64([2064, 2065.5, 3000.25, 4800, 9000.75, 14328]) / 48000.0).astype(np.float32)
+    gains = np.float32([0.5, -0.7, 0.9, 0.3, 0.6, -0.95])
+    for i in range(n):
+        delay.delay_time.set_value(delays[i], instance=i)
+        fb.gain.set_value(gains[i], instance=i)
+    s.connect(delay)
+    delay.connect(bq).connect(fb).connect(delay)
+    bq.connect(c.destination())
+    s.connect(c.destination())
+    return c
+
+
+def g_feed_forward_echo(be):    # 256 contexts: one per CU, the ring kernel with nothing fed back
+    c = _ctx(be, n=256, frames=2048 * 2)
+    s = c.create_buffer_source()
+    s.set_buffer_batch(np.zeros((256, 1, 2048 * 2), np.float32), SR)
+    s.start()
+    s.connect(c.destination())
+    s.connect(c.create_delay(0.4, delay_time=0.1)).connect(c.create_gain(gain=0.5)).connect(c.destination())
+    return c
+
+
+def g_delay_gather(be):         # a delay in front of a convolver keeps the gather kernel
+    c = _ctx(be)
+    s = _source(c)
+    d = c.create_delay(1.0, delay_time=0.05)
+    s.connect(d).connect(c.create_convolver(buffer=waa.AudioBuffer(np.ones((1, 300), np.float32), SR))).connect(c.destination())
+    return c
+
+
+def _frozen_loop(be, kind, delay_time):
+    """a burst -> Delay -> oversampled WaveShaper / HRTF panner -> Gain -> back (tests/test_frozen_loops.py): dynamic counts, the
+    loop cut at the node and launched quantum block by quantum block"""
+    n, frames = 3, RQ * 70 + 33
+    c = _ctx(be, n=n, frames=frames)
+    s = c.create_buffer_source()
+    s.set_buffer_batch(white_noise(n, 2, RQ * 20 + 7, seed0=5) * np.float32(0.6), SR)
+    d = c.create_delay(0.1, delay_time=delay_time)
+    f = (c.create_panner(panning_model="HRTF", position=(0.8, 0.3, -0.6)) if kind == "hrtf"
+         else c.create_wave_shaper(curve=CURVE, oversample=kind))
+    s.connect(d)
+    d.connect(f).connect(c.create_gain(gain=0.45)).connect(d)
+    f.connect(c.destination())
+    for i in range(n):
+        s.start_at(i * 211.0 / SR, instance=i)
+    return c
+
+
+def g_qloop_shaper_2x(be):
+    return _frozen_loop(be, "2x", 0.01)
+
+
+def g_qloop_hrtf(be):
+    return _frozen_loop(be, "hrtf", 0.01)
+
+
+def g_qloop_automated(be):
+    """... with an a-rate delayTime, an automated Biquad and a gain modulated from outside: their launches run once in front of
+    the quantum blocks"""
+    n, frames = 3, RQ * 70 + 33
+    c = _ctx(be, n=n, frames=frames)
+    s = _source(c, frames=RQ * 40, seed0=21, scale=0.5)
+    d = c.create_delay(0.05, delay_time=0.01)
+    d.delay_time.set_value_at_time(0.004, 0.0).linear_ramp_to_value_at_time(0.03, frames / SR)
+    sh = c.create_wave_shaper(curve=CURVE, oversample="2x")
+    bq = c.create_biquad_filter(type_="bandpass", frequency=800.0, q=1.5)
+    bq.frequency.set_value_at_time(300.0, 0.0).exponential_ramp_to_value_at_time(4000.0, frames / SR)
+    g = c.create_gain(gain=0.35)
+    lfo = c.create_oscillator(type_="sine", frequency=7.0)
+    lfo.connect(c.create_gain(gain=0.1)).connect(g.gain)
+    lfo.start()
+    s.connect(d)
+    d.connect(sh).connect(bq).connect(g).connect(d)
+    bq.connect(c.destination())
+    return c
+
+
+def g_qloop_conv_and_shaper(be):
+    n, frames = 3, RQ * 70 + 33
+    c = _ctx(be, n=n, frames=frames)
+    s = _source(c, frames=RQ * 30, seed0=33, scale=0.4)
+    d = c.create_delay(0.1, delay_time=0.005)
+    cv = c.create_convolver(buffer=waa.AudioBuffer(_decaying_ir(2, 300, 7), SR))
+    sh = c.create_wave_shaper(curve=CURVE, oversample="2x")
+    s.connect(d)
+    d.connect(cv).connect(sh).connect(c.create_gain(gain=0.25)).connect(d)
+    sh.connect(c.destination())
+    return c
+
+
+def g_qloop_long_conv_refused(be):  # partitions that span several quanta in a short loop: status 4
+    c = _ctx(be, n=1, frames=RQ * 70 + 33)
+    s = _source(c, frames=RQ * 9 + 3)
+    d = c.create_delay(0.1, delay_time=0.003)
+    cv = c.create_convolver(buffer=waa.AudioBuffer(_decaying_ir(2, 5000, 1), SR))
+    s.connect(d)
+    d.connect(cv).connect(c.create_gain(gain=0.3)).connect(d)
+    cv.connect(c.destination())
+    return c
+
+
+def g_oversampled_shaper(be):   # outside any loop, static counts: the transform form in one launch (under WAA_OS_MATRIX: two qgemm stages)
+    c = _ctx(be, frames=RQ * 40)
+    _source(c).connect(c.create_wave_shaper(curve=CURVE, oversample="4x")).connect(c.destination())
+    return c
+
+
+def g_listener_automated_in_a_loop(be):  # ... the panner inside a block-scheduled loop: the geometry runs once in front of the blocks
+    c = _ctx(be)
+    c.listener().position_x.set_value_at_time(0.0, 0.0).linear_ramp_to_value_at_time(1.0, 0.3)
+    s = _source(c)
+    d = c.create_delay(1.0, delay_time=0.05)
+    s.connect(d)
+    d.connect(c.create_panner(panning_model="equalpower", position=(1.0, 0.0, -1.0))).connect(c.create_gain(gain=0.4)).connect(d)
+    d.connect(c.destination())
+    return c
+
+
+def g_biquad_k_rate(be):
+    ctx, nodes = c2(be, white_noise(1, 2, RQ * 20), device=waa.PLAN_ONLY)
+    nodes["biquad"].frequency.set_block(0, np.linspace(100, 1000, 20).astype(np.float32))
+    return ctx
+
+
+def g_biquad_a_rate_shared(be):  # one shared coefficient table: coefs, hp digest, tile digests, lanes
+    ctx, nodes = c2(be, white_noise(3, 2, 2048 * 3 + 50), device=waa.PLAN_ONLY)
+    nodes["biquad"].frequency.set_value_at_time(10.0, 0.0).exponential_ramp_to_value_at_time(10000.0, 0.05)
+    return ctx
+
+
+def g_iir(be):
+    c = _ctx(be, frames=RQ * 64)
+    _source(c).connect(c.create_iir_filter([0.2, 0.3, 0.1], [1.0, -0.5, 0.2])).connect(c.destination())
+    return c
+
+
+def g_fm_pair(be):
+    c = _ctx(be, n=3, frames=RQ * 40)
+    mod, idx, car = c.create_oscillator(type_="sine", frequency=110.0), c.create_gain(gain=300.0), c.create_oscillator(type_="sine", frequency=440.0)
+    for i in range(3):
+        car.detune.set_value(25.0 * i, instance=i)
+    mod.connect(idx).connect(car.frequency)
+    car.connect(c.destination())
+    mod.start()
+    car.start_at(0.001)
+    return c
+
+
+def g_compressor(be):
+    c = _ctx(be, n=2, frames=RQ * 64)
+    _source(c).connect(c.create_dynamics_compressor()).connect(c.destination())
+    return c
+
+
+def g_compressor_behind_an_echo_loop(be):  # a kind the echo-tail fusion does not know: the fusion leaves the whole plan alone
+    c = _ctx(be)
+    s = _source(c)
+    d = c.create_delay(1.0, delay_time=0.05)
+    s.connect(d)
+    d.connect(c.create_gain(gain=0.5)).connect(d)
+    mix = c.create_gain(gain=1.0)
+    d.connect(mix)
+    s.connect(mix)
+    mix.connect(c.create_dynamics_compressor()).connect(c.destination())
+    return c
+
+
+def g_splitter_merger(be):      # swap the channels: splitter -> merger
+    c = _ctx(be, frames=RQ * 30)
+    s = _source(c)
+    sp, mg = c.create_channel_splitter(2), c.create_channel_merger(2)
+    s.connect(sp)
+    sp.connect(mg, 0, 1)
+    sp.connect(c.create_gain(gain=0.5), 1).connect(mg, 0, 0)
+    mg.connect(c.destination())
+    return c
+
+
+def g_merger_behind_an_echo_loop(be):
+    c = _ctx(be)
+    s = _source(c, n_ch=1)
+    d = c.create_delay(1.0, delay_time=0.05)
+    s.connect(d)
+    d.connect(c.create_gain(gain=0.5)).connect(d)
+    mg = c.create_channel_merger(2)
+    d.connect(mg, 0, 0)
+    s.connect(mg, 0, 1)
+    mg.connect(c.destination())
+    return c
+
+
+def _per_instance_conv(be, taps):
+    n, frames = 3, RQ * 40
+    c = _ctx(be, n=n, frames=frames)
+    conv = c.create_convolver()
+    conv.set_buffer_batch(np.stack([_decaying_ir(2, taps, 100 + 7 * i) for i in range(n)]), SR)
+    _source(c).connect(conv).connect(c.destination())
+    return c
+
+
+def g_per_instance_conv_direct(be):
+    return _per_instance_conv(be, 100)
+
+
+def g_per_instance_conv_fft(be):
+    return _per_instance_conv(be, 1500)
+
+
+def g_block_loop_zero_conv(be):  # the fill inside a block-scheduled loop: once in front of the blocks
+    c = _ctx(be, frames=2048 * 6)
+    s = _source(c)
+    d = c.create_delay(0.1, delay_time=0.06)
+    cv = c.create_convolver(buffer=waa.AudioBuffer(np.zeros((2, 64), np.float32), SR))
+    s.connect(d)
+    d.connect(cv).connect(c.create_gain(gain=0.3)).connect(d)
+    d.connect(c.destination())
+    return c
+
+
+def g_misordered_refused(be):   # (with WAA_DEBUG_REVERSE_PLAN: the validator's refusal and its message)
+    c = _ctx(be, n=2, frames=RQ * 40)
+    s = _source(c)
+    conv = c.create_convolver(buffer=waa.AudioBuffer(white_noise(1, 2, 300)[0], SR))
+    s.connect(c.create_biquad_filter(type_="lowpass", frequency=500.0)).connect(conv).connect(c.create_stereo_panner(pan=0.3)).connect(c.destination())
+    return c
+
+
+def g_timeline(be, device=waa.PLAN_ONLY):
+    """a gain with another automation per context: replayed on the device where there is one (StepKind::Timeline), evaluated on
+    the host by a plan-only batch"""
+    c = _ctx(be, frames=RQ * 40, device=device)
+    g = c.create_gain(gain=0.5)
+    for i in range(3):
+        g.gain.set_value_at_time(0.1 * (i + 1), 0.0, instance=i).linear_ramp_to_value_at_time(1.0, 0.05 + 0.01 * i, instance=i)
+    _source(c).connect(g).connect(c.destination())
+    return c
+
+
+# name -> (builder, measurement switches on top of WAA_PLAN_LAUNCHES)
+NAMED = {
+    "c2": (g_c2, {}), "t1": (g_t1, {}), "c4": (g_c4, {}), "c5": (g_c5, {}),
+    "echo_ring": (g_echo_ring, {}), "echo_ring_tail": (g_echo_ring_tail, {}),
+    "loop_kernel": (g_loop_kernel, {}), "loop_kernel_shaper": (g_loop_kernel_shaper, {}),
+    "two_block_loops": (g_two_block_loops, {}), "block_loop_automated": (g_block_loop_automated, {}),
+    "block_loop_zero_conv": (g_block_loop_zero_conv, {}), "listener_automated_in_a_loop": (g_listener_automated_in_a_loop, {}),
+    "filtered_echo_tail": (g_filtered_echo_tail, {}), "feed_forward_echo": (g_feed_forward_echo, {}), "delay_gather": (g_delay_gather, {}),
+    "qloop_shaper_2x": (g_qloop_shaper_2x, {}), "qloop_hrtf": (g_qloop_hrtf, {}), "qloop_automated": (g_qloop_automated, {}),
+    "qloop_conv_and_shaper": (g_qloop_conv_and_shaper, {}),
+    "qloop_long_conv_refused": (g_qloop_long_conv_refused, {}), "frozen_loop_refused": (g_qloop_shaper_2x, {"WAA_NO_FROZEN_LOOPS": "1"}),
+    "oversampled_shaper_matrix": (g_oversampled_shaper, {"WAA_OS_MATRIX": "1"}),
+    "biquad_k_rate": (g_biquad_k_rate, {}), "biquad_a_rate_shared": (g_biquad_a_rate_shared, {}), "iir": (g_iir, {}),
+    "fm_pair": (g_fm_pair, {}),
+    "compressor": (g_compressor, {}), "compressor_behind_an_echo_loop": (g_compressor_behind_an_echo_loop, {}),
+    "splitter_merger": (g_splitter_merger, {}), "merger_behind_an_echo_loop": (g_merger_behind_an_echo_loop, {}),
+    "per_instance_conv_direct": (g_per_instance_conv_direct, {}), "per_instance_conv_fft": (g_per_instance_conv_fft, {}),
+}
+
+
+def random_graph(seed, frozen):
+    def build(be):
+        c, _ = build_random_graph(be, seed, frozen=frozen)
+        c.device = waa.PLAN_ONLY
+        return c
+    return build
+
+
+# the 60 seeds of test_random_graphs_plan_on_cpu, plain and with frozen-state nodes
+RANDOM = {f"seed {seed}{' frozen' if frozen else ''}": (random_graph(seed, frozen), {}) for frozen in (False, True) for seed in range(60)}
+
+
+def describe(be, build, switches, setenv, delenv):
+    """the plan text with the launch list behind it, the first line's timing tail cut off; a refusal as its status and message"""
+    setenv("WAA_PLAN_LAUNCHES", "1")
+    for k, v in switches.items():
+        setenv(k, v)
+    try:
+        c = build(be)
+        try:
+            text = c.plan_describe()
+        except waa.WaaError as e:
+            text = f"refused with status {e.status}: {e}\n"
+        c.close()
+    finally:
+        for k in switches:
+            delenv(k)
+    first, _, rest = text.partition("\n")
+    return first.split(" | timing:")[0] + "\n" + rest
+
+
+def _sections(text):
+    out, name = {}, None
+    for line in text.splitlines(keepends=True):
+        if line.startswith("==== "):
+            name = line[5:].rstrip("\n")
+            out[name] = ""
+        else:
+            out[name] += line
+    return out
+
+
+def _kind_list(text):
+    kinds = []
+    for m in re.finditer(r"^launch \d+: kind (\d+) (\S+) ", text, re.M):
+        assert KIND_NAMES[int(m.group(1))] == m.group(2), m.group(0)
+        kinds.append(int(m.group(1)))
+    return kinds
+
+
+def named_text(be, setenv, delenv):
+    """named.txt: the full text of every named graph, a section each"""
+    return "".join(f"==== {name}\n{describe(be, build, switches, setenv, delenv)}" for name, (build, switches) in NAMED.items())
+
+
+def random_line(name, text):
+    """random.txt holds one line per random graph instead of its text (120 texts are 260 KB): the SHA-256 of the full text, which
+    the comparison is made on, and the kinds of its launches in order, for a reader and for the coverage test"""
+    what = "refused" if text.startswith("refused") else "kinds " + ",".join(str(k) for k in _kind_list(text))
+    return f"{name}: sha256 {hashlib.sha256(text.encode()).hexdigest()} {what}\n"
+
+
+def _golden(name):
+    with open(os.path.join(GOLDEN, name + ".txt")) as f:
+        return f.read()
+
+
+def test_named_launch_lists_are_what_they_were(hip, monkeypatch):
+    want = _sections(_golden("named"))
+    assert list(want) == list(NAMED)
+    for name, (build, switches) in NAMED.items():
+        got = describe(hip, build, switches, monkeypatch.setenv, monkeypatch.delenv)
+        assert got == want[name], name
+        assert "\nlaunch 0: " in got or (name.endswith("_refused") and got.startswith("refused with status 4:")), got
+
+
+def test_random_launch_lists_are_what_they_were(hip, monkeypatch):
+    want = _golden("random").splitlines(keepends=True)
+    assert len(want) == len(RANDOM)
+    planned = 0
+    for (name, (build, switches)), line in zip(RANDOM.items(), want):
+        got = describe(hip, build, switches, monkeypatch.setenv, monkeypatch.delenv)
+        assert random_line(name, got) == line, got   # (the text that differs: compare with the same dump of the parent commit)
+        assert got.startswith(("batch:", "refused with status 4:")), got
+        planned += "\nlaunch 0: " in got
+    assert planned >= 80
+
+
+def test_the_validator_names_the_kind_it_refuses(hip, monkeypatch):
+    """(a reversed launch list, as in tests/test_plan.py: the message keeps the number and says what it stands for)"""
+    got = describe(hip, g_misordered_refused, {"WAA_DEBUG_REVERSE_PLAN": "1"}, monkeypatch.setenv, monkeypatch.delenv)
+    assert re.fullmatch(r"refused with status 3: internal: launch 0 of the plan \(kind (\d+), (\w+)\) reads a buffer that a later launch produces\n", got), got
+    m = re.search(r"kind (\d+), (\w+)", got)
+    assert KIND_NAMES[int(m.group(1))] == m.group(2)
+
+
+def test_the_corpus_reaches_every_kind_and_every_loop_form():
+    """over the expected files, which the tests above hold the planner to (the device-planned Timeline graph:
+    test_launch_list_of_device_side_automation)"""
+    named = _golden("named")
+    cpu = set(_kind_list(named))
+    for line in _golden("random").splitlines():
+        if " kinds " in line:
+            cpu |= {int(k) for k in line.rsplit(" kinds ", 1)[1].split(",") if k}
+    assert cpu == set(range(len(KIND_NAMES))) - {KIND_NAMES.index("timeline")}
+    assert cpu | set(_kind_list(_golden("device"))) == set(range(len(KIND_NAMES)))
+    launches = [l for l in named.splitlines() if l.startswith("launch ")]
+    for form in ("group=0 ", "group=1 ", "qgroup=0 ", "prologue=1 ", "fused=1 ", "ff=1 ", "fb=0 ", "tail="):
+        assert any(form in l and not (form == "tail=" and "tail=-1" in l) for l in launches), form
+    for k, name in enumerate(KIND_NAMES):   # every kind that may run once in front of a loop's blocks does so somewhere
+        if name in ("zero_fill", "biquad_coefs", "biquad_hp", "panner_geom", "biquad_tile_digest", "chain"):
+            assert any(f"kind {k} {name} " in l and "prologue=1" in l for l in launches), name
+    for name in ("dyn", "link", "hrtf", "os_fft", "conv_fft", "conv_codes"):   # the ranged kinds, each inside a quantum-blocked loop
+        assert any(f" {name} " in l and "qgroup=-1" not in l and "prologue=0" in l for l in launches), name
+    assert any(l.startswith("group_tiles: ") for l in named.splitlines()) and any(l.startswith("qgroup_quanta: ") for l in named.splitlines())
+
+
+@pytest.mark.gpu
+def test_launch_list_of_device_side_automation(hip, monkeypatch):
+    """per-context automation is replayed on the device (StepKind::Timeline) only by a batch that has one"""
+    got = describe(hip, lambda be: g_timeline(be, device=0), {}, monkeypatch.setenv, monkeypatch.delenv)
+    assert got == _sections(_golden("device"))["timeline"]
+    assert KIND_NAMES.index("timeline") in _kind_list(got)

@@ -970,7 +970,6 @@ waa_status waa_set_param_block(waa_batch* b, uint32_t node, uint32_t param, uint
 
 // build_plan under a stopwatch; the split (hipMalloc / blocking uploads / the rest = host planning: ordering, scheduling
 // replay, coefficient and automation evaluation) goes into the plan description
-static int run_steps(waa_batch* b);
 int waa_settle_loops(waa_batch* b);
 
 // AudioBufferSourceNode::playback_rate / detune with an input from the graph (k-rate: value + the first sample of the
@@ -1314,6 +1313,23 @@ waa_status waa_plan_describe(waa_batch* b, char* buf, size_t cap, size_t* needed
            b->t_plan_ms - b->plan_alloc_ms - b->plan_upload_ms);
   text += head;
   for (auto& l : b->plan_log) text += l + "\n";
+  if (measure_switch("WAA_PLAN_LAUNCHES")) {
+    // the launch list itself, one positional line per step (no pointers): what the planner's loop handling and fusions decide
+    // and the plan log does not show (tests/test_launch_list.py)
+    char line[320];
+    for (size_t k = 0; k < b->steps.size(); k++) {
+      const Step& st = b->steps[k];
+      snprintf(line, sizeof line, "launch %zu: kind %d %s group=%d qgroup=%d prologue=%d fused=%d ff=%d fb=%d tail=%d cmax=%d slots=%d,%d,%d,%d\n", k,
+               (int)st.kind, step_traits(st.kind).name, st.group, st.qgroup, (int)st.prologue, (int)st.echo_fused, (int)st.echo_ff, st.echo_fb,
+               st.echo_tail_step, st.cmax, st.profile_slot, st.slot_fwd, st.slot_mac, st.slot_inv);
+      text += line;
+    }
+    text += "group_tiles:";
+    for (uint32_t t : b->group_tiles) text += " " + std::to_string(t);
+    text += "\nqgroup_quanta:";
+    for (uint32_t q : b->qgroup_quanta) text += " " + std::to_string(q);
+    text += "\n";
+  }
   if (needed) *needed = text.size();
   if (buf && cap) {
     const size_t n = std::min(cap - 1, text.size());
@@ -1446,274 +1462,6 @@ waa_status waa_render(waa_batch* b) {
   }
   b->rendered = true;
   return run_steps(b);
-}
-
-// the launches of the current plan, from the initial state
-static int run_steps(waa_batch* b) {
-  // every render starts from the initial state (offline contexts render exactly once; re-rendering the
-  // same batch is what the benchmark loop does)
-  for (auto& sb : b->state_bufs) HIP_TRY(hipMemsetAsync(sb.first, 0, sb.second, b->stream));
-  for (auto& sb : b->ones_bufs) HIP_TRY(hipMemsetAsync(sb.first, 0xFF, sb.second, b->stream));
-  for (auto& n : b->nodes) n.an = Node::AnBatch{};
-  for (auto& v : b->scan_issued) v = 0;
-  auto timed = [&](int slot, auto&& launch) -> int {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (b->profiling && slot >= 0) {
-      HIP_TRY(hipEventCreate(&e0));
-      HIP_TRY(hipEventCreate(&e1));
-      HIP_TRY(hipEventRecord(e0, b->stream));
-    }
-    launch();
-    {
-      const hipError_t le = hipGetLastError();
-      if (le != hipSuccess)
-        return fail(WAA_ERR_DEVICE, "launch of %s failed: %s", slot >= 0 ? b->prof[slot].name.c_str() : "a kernel without a profile slot",
-                    hipGetErrorString(le));
-    }
-    if (b->profiling && slot >= 0) {
-      HIP_TRY(hipEventRecord(e1, b->stream));
-      b->prof[slot].pending.push_back({e0, e1});
-    }
-    return 0;
-  };
-  // one step over the tile range [t0, t1)
-  auto run_step = [&](const Step& st, uint32_t t0, uint32_t t1) -> int {
-    int e = 0;
-    switch (st.kind) {
-      case 1: {
-        BiquadStreamDesc d = st.bq;
-        d.tile0 = t0;
-        d.tile1 = t1;
-        if (st.scan.payload) {
-          e = timed(st.profile_slot, [&] { launch_biquad_scan(d, st.scan, b->scan_issued, b->stream); });
-        } else {
-          e = timed(st.profile_slot, [&] { launch_biquad_stream(d, b->stream); });
-        }
-        break;
-      }
-      case 2: {
-        // (inside a block-scheduled feedback loop: the partitions of this tile range; loop_block_tiles made the range a
-        // whole number of them)
-        ConvDesc d = st.conv;
-        d.kb0 = (int)std::min<uint64_t>((uint64_t)t0 * TILE / (uint64_t)d.block, (uint64_t)d.nb);
-        d.kb1 = (int)std::min<uint64_t>(((uint64_t)t1 * TILE + (uint64_t)d.block - 1) / (uint64_t)d.block, (uint64_t)d.nb);
-        if (d.kb1 <= d.kb0) break;
-        if ((e = timed(st.slot_fwd, [&] { launch_conv_forward(d, b->stream); }))) break;
-        if ((e = timed(st.slot_mac, [&] { d.per_inst ? launch_conv_inst_mac(d, b->stream) : launch_conv_mac(d, b->stream); }))) break;
-        e = timed(st.slot_inv, [&] { launch_conv_inverse(d, b->stream); });
-        break;
-      }
-      case 3: HIP_TRY(hipMemsetAsync(st.zero_ptr, 0, st.zero_bytes, b->stream)); break;
-      case 4: {
-        ConvDesc d = st.conv;
-        d.kb0 = (int)std::min<uint64_t>((uint64_t)t0 * (TILE / 1024), (uint64_t)st.conv.kb1);
-        d.kb1 = (int)std::min<uint64_t>((uint64_t)t1 * (TILE / 1024), (uint64_t)st.conv.kb1);
-        if (d.kb1 <= d.kb0) break;
-        e = timed(st.slot_mac, [&] { d.per_inst ? launch_conv_inst_direct(d, b->stream) : launch_conv_direct(d, b->stream); });
-        break;
-      }
-      case 5: e = timed(st.profile_slot, [&] { launch_biquad_coefs(st.coef, b->stream); }); break;
-      case 6: {
-        IirStreamDesc d = st.iir;
-        d.tile0 = t0;
-        d.tile1 = t1;
-        e = timed(st.profile_slot, [&] { launch_iir_stream(d, b->stream); });
-        break;
-      }
-      case 7: {
-        DelayDesc d = st.delay;
-        d.tile0 = t0;
-        d.tile1 = t1;
-        e = timed(st.profile_slot, [&] { launch_delay(d, b->stream); });
-        break;
-      }
-      case 8: e = timed(st.profile_slot, [&] { launch_loop(st.loop, b->stream); }); break;
-      case 9: e = timed(st.profile_slot, [&] { launch_osc(st.osc, b->stream); }); break;
-      case 10: e = timed(st.profile_slot, [&] { launch_dyn(st.dyn, b->stream); }); break;
-      case 11: e = timed(st.profile_slot, [&] { launch_conv_codes(st.ccode, b->stream); }); break;
-      case 13: e = timed(st.profile_slot, [&] { launch_panner_geom(st.geom, b->stream); }); break;
-      case 14: e = timed(st.profile_slot, [&] { launch_timeline(st.tl, b->stream); }); break;
-      case 15: e = timed(st.profile_slot, [&] { launch_link(st.link, b->stream); }); break;
-      case 16: e = timed(st.profile_slot, [&] { launch_qgemm(st.qgemm, b->stream); }); break;
-      case 17: e = timed(st.profile_slot, [&] { launch_hrtf(st.hrtf, b->stream); }); break;
-      case 20: e = timed(st.profile_slot, [&] { launch_osfft(st.osfft, b->stream); }); break;
-      case 22: e = timed(st.profile_slot, [&] { launch_route(st.route, b->stream); }); break;  // (never inside a feedback loop)
-      case 21:  // (never inside a feedback loop: always the whole render)
-        if ((e = timed(st.slot_fwd, [&] { launch_compressor_level(st.comp, b->stream); }))) break;
-        if ((e = timed(st.slot_mac, [&] { launch_compressor_detector(st.comp, b->stream); }))) break;
-        e = timed(st.slot_inv, [&] { launch_compressor_apply(st.comp, b->stream); });
-        break;
-      case 12:
-        if (st.hp.coefs) e = timed(st.profile_slot, [&] { launch_biquad_hp(st.hp, b->stream); });
-        break;
-      case 18: e = timed(st.profile_slot, [&] { launch_biquad_tile_digest(st.lanes, b->stream); }); break;
-      case 19: {
-        BiquadLanesDesc d = st.lanes;
-        d.tile0 = t0;
-        d.tile1 = t1;
-        e = timed(st.profile_slot, [&] { launch_biquad_lanes(d, b->stream); });
-        break;
-      }
-      default: {
-        if (st.echo_ff && t0 == 0 && t1 == b->n_tiles) {  // the feed-forward echo out of the LDS ring (waa_echo.hip)
-          ChainDesc d = st.echo_line;
-          d.tile0 = t0;
-          d.tile1 = t1;
-          e = timed(st.profile_slot, [&] { launch_echo_ring(d, d.n_inputs, st.echo_chunk, st.echo_ring, &st.echo_tail, b->stream); });
-          break;
-        }
-        ChainDesc d = st.chain;
-        d.tile0 = t0;
-        d.tile1 = t1;
-        e = timed(st.profile_slot, [&] { launch_chain(d, st.cmax, b->stream); });
-        break;
-      }
-    }
-    return e;
-  };
-  // one ranged step of a quantum-blocked loop (dynamic-count plans): only the kinds the planner puts there
-  auto run_step_q = [&](const Step& st, uint32_t q0, uint32_t q1) -> int {
-    switch (st.kind) {
-      case 10: {
-        DynDesc d = st.dyn;
-        d.q0 = q0;
-        d.q1 = q1;
-        return timed(st.profile_slot, [&] { launch_dyn(d, b->stream); });
-      }
-      case 15: {
-        LinkDesc d = st.link;
-        d.q0 = q0;
-        d.q1 = q1;
-        return timed(st.profile_slot, [&] { launch_link(d, b->stream); });
-      }
-      case 17: {
-        HrtfDesc d = st.hrtf;
-        d.q0 = q0;
-        d.q1 = q1;
-        return timed(st.profile_slot, [&] { launch_hrtf(d, b->stream); });
-      }
-      case 20: {
-        OsFftDesc d = st.osfft;
-        d.q0 = q0;
-        d.q1 = q1;
-        return timed(st.profile_slot, [&] { launch_osfft(d, b->stream); });
-      }
-      case 2: {  // a ConvolverNode with 128-frame partitions: block k of its transforms IS render quantum k
-        ConvDesc d = st.conv;
-        if (d.block != RQ) return fail(WAA_ERR_INVALID_STATE, "internal: a convolver with %d-frame partitions inside a quantum-blocked loop", d.block);
-        d.kb0 = (int)std::min<uint32_t>(q0, (uint32_t)d.nb);
-        d.kb1 = (int)std::min<uint32_t>(q1, (uint32_t)d.nb);
-        if (d.kb1 <= d.kb0) return 0;
-        if (int e = timed(st.slot_fwd, [&] { launch_conv_forward(d, b->stream); })) return e;
-        if (int e = timed(st.slot_mac, [&] { launch_conv_mac(d, b->stream); })) return e;
-        return timed(st.slot_inv, [&] { launch_conv_inverse(d, b->stream); });
-      }
-      case 11: {
-        ConvCodeDesc d = st.ccode;
-        d.q0 = q0;
-        d.q1 = q1;
-        return timed(st.profile_slot, [&] { launch_conv_codes(d, b->stream); });
-      }
-      default: return fail(WAA_ERR_INVALID_STATE, "internal: step kind %d inside a quantum-blocked loop", st.kind);
-    }
-  };
-  for (size_t i = 0; i < b->steps.size();) {
-    const Step& st = b->steps[i];
-    if (st.qgroup >= 0) {
-      // a feedback loop cut at frozen-state nodes: its launches in order, over the same few quanta each, block after block
-      size_t j = i;
-      while (j < b->steps.size() && b->steps[j].qgroup == st.qgroup) j++;
-      for (size_t k = i; k < j; k++)
-        if (b->steps[k].prologue) {  // param tables and chains that only depend on data from outside the loop: once, whole render
-          int e = run_step(b->steps[k], 0, b->n_tiles);
-          if (e) return e;
-        }
-      const uint32_t bq = b->loops_one_quantum ? 1u : std::max<uint32_t>(1, b->qgroup_quanta[(size_t)st.qgroup]);
-      if (bq > 1) b->loops_unsettled = true;
-      // (the first block is one quantum: every delay line starts as one silent channel, so the count moves in quantum 0 of
-      // nearly every graph — and a change in a block's LAST quantum is the one place where it is harmless)
-      for (uint32_t q0 = 0; q0 < b->n_quanta;) {
-        const uint32_t q1 = std::min<uint32_t>(b->n_quanta, q0 + (q0 == 0 ? 1u : bq));
-        for (size_t k = i; k < j; k++) {
-          if (b->steps[k].prologue) continue;
-          int e = run_step_q(b->steps[k], q0, q1);
-          if (e) return e;
-        }
-        q0 = q1;
-      }
-      i = j;
-      continue;
-    }
-    if (st.group < 0) {
-      if (!st.echo_fused) {  // (a fused tail was rendered by its loop's launch)
-        int e = run_step(st, 0, b->n_tiles);
-        if (e) return e;
-      }
-      i++;
-      continue;
-    }
-    // block-scheduled feedback loop: steps [i, j) block by block (graph.rs cycle breaker, see build_plan)
-    size_t j = i;
-    while (j < b->steps.size() && b->steps[j].group == st.group) j++;
-    for (size_t k = i; k < j; k++)
-      if (b->steps[k].prologue) {
-        int e = run_step(b->steps[k], 0, b->n_tiles);
-        if (e) return e;
-      }
-    const uint32_t bt = b->group_tiles[st.group];
-    {
-      // a loop that is ONE element-wise launch per block (the echo loop): one persistent launch can walk the blocks itself
-      // (WAA_PERSISTENT_LOOP=1).  Measured on the fb workload (1024 contexts x 10 s, 47 blocks): 5.17-5.20 ms against
-      // 5.19-5.37 ms for the 47 launches — the loop is bound by its 3 x 3.9 GB per pass at 16 wavefronts per CU, not by the
-      // launches; opt-in, parity-tested (tests/test_cycles.py), not the default.
-      size_t n_body = 0, body = 0;
-      for (size_t k = i; k < j; k++)
-        if (!b->steps[k].prologue && !b->steps[k].echo_fused) {  // (fused: body launches the ring kernel's BQ form stands for)
-          n_body++;
-          body = k;
-        }
-      if (n_body == 1 && b->steps[body].kind == 0 && b->steps[body].echo_fb >= 0) {  // (decided by the planner)
-        // the echo loop with its delay line in LDS: the whole loop in one launch (waa_echo.hip)
-        const Step& bs = b->steps[body];
-        ChainDesc d = bs.chain;
-        d.tile0 = 0;
-        d.tile1 = b->n_tiles;
-        int e = timed(bs.profile_slot, [&] {
-          launch_echo_ring(d, bs.echo_fb, bs.echo_chunk, bs.echo_ring, bs.echo_tail_step >= 0 ? &bs.echo_tail : nullptr, b->stream,
-                           bs.echo_bq.coefs ? &bs.echo_bq : nullptr);
-        });
-        if (e) return e;
-        i = j;
-        continue;
-      }
-      if (n_body == 1 && b->steps[body].kind == 0 && b->steps[body].cmax <= 2 && measure_switch("WAA_PERSISTENT_LOOP")) {
-        const Step& bs = b->steps[body];
-        bool element_wise = true;
-        for (int o = 0; o < bs.chain.n_ops; o++) element_wise &= bs.chain.ops[o].kind != OP_BIQUAD;
-        int curve_op = -1;
-        if (element_wise && !resample_shape(bs.chain, &curve_op)) {
-          ChainDesc d = bs.chain;
-          d.tile0 = 0;
-          d.tile1 = b->n_tiles;
-          d.persist_block = bt * (TILE / 256);
-          int e = timed(bs.profile_slot, [&] { launch_chain(d, bs.cmax, b->stream); });
-          if (e) return e;
-          i = j;
-          continue;
-        }
-      }
-    }
-    for (uint32_t t0 = 0; t0 < b->n_tiles; t0 += bt) {
-      const uint32_t t1 = std::min(b->n_tiles, t0 + bt);
-      for (size_t k = i; k < j; k++)
-        if (!b->steps[k].prologue && !b->steps[k].echo_fused) {
-          int e = run_step(b->steps[k], t0, t1);
-          if (e) return e;
-        }
-    }
-    i = j;
-  }
-  return WAA_OK;
 }
 
 static int drain_profile(waa_batch* b) {

@@ -197,7 +197,7 @@ static int plan_link(waa_batch* b, uint32_t id, int kind, int src_id, uint32_t t
     n.code = d_out;
   }
   Step st;
-  st.kind = 15;
+  st.kind = StepKind::Link;
   LinkDesc& d = st.link;
   std::memset(&d, 0, sizeof d);
   d.in_code = d_in;
@@ -250,7 +250,7 @@ int plan_oversampler(waa_batch* b, uint32_t id, int src_id) {
     uint32_t seg_len = 0, n_seg = 0;
     for (int c0 = 0; c0 < nch; c0 += 2) {
       Step os;
-      os.kind = 20;
+      os.kind = StepKind::OsFft;
       OsFftDesc& f = os.osfft;
       std::memset(&f, 0, sizeof f);
       f.src = in_sig.base + (uint64_t)c0 * in_sig.ch_stride;
@@ -297,7 +297,7 @@ int plan_oversampler(waa_batch* b, uint32_t id, int src_id) {
       (e = dev_alloc(b, &sbuf, (size_t)b->n_inst * nch * b->n_quanta * up_len)))
     return e;
   Step up;
-  up.kind = 16;
+  up.kind = StepKind::QGemm;
   QGemmDesc& g = up.qgemm;
   std::memset(&g, 0, sizeof g);
   g.A = d_up;
@@ -324,7 +324,7 @@ int plan_oversampler(waa_batch* b, uint32_t id, int src_id) {
   up.loop_writes.push_back(sbuf);
   b->steps.push_back(up);
   Step dn;
-  dn.kind = 16;
+  dn.kind = StepKind::QGemm;
   QGemmDesc& h = dn.qgemm;
   std::memset(&h, 0, sizeof h);
   h.A = d_dn;
@@ -590,7 +590,7 @@ int plan_hrtf(waa_batch* b, uint32_t id, int src_id) {
     if ((e = dev_upload(b, &d_hstatic, hs))) return e;
   }
   Step st;
-  st.kind = 17;
+  st.kind = StepKind::Hrtf;
   HrtfDesc& d = st.hrtf;
   std::memset(&d, 0, sizeof d);
   d.in = in_sig;

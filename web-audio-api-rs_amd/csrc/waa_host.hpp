@@ -1,5 +1,5 @@
 // waa_host.hpp — host-side data model of libwaa_hip.so shared by the scheduler (waa_schedule.cpp), the planner
-// (waa_plan.cpp) and the C ABI (waa_abi.cpp).  Not part of the public interface (include/waa_hip.h).
+// (waa_plan.cpp), the executor (waa_run.cpp) and the C ABI (waa_abi.cpp).  Not part of the public interface (include/waa_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -245,12 +245,82 @@ struct ProfileEntry {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// What a launch of the plan is.  The numbers are fixed: internal error messages and the launch-list dump (WAA_PLAN_LAUNCHES) print them.
+enum class StepKind : int {
+  Chain = 0,              // interpreter kernel over a chain of element-wise ops (or the LDS-ring kernel: Step::echo_fb / echo_ff)
+  BiquadStream = 1,       // streaming biquad kernel; with Step::scan.payload its time-parallel form (waa_biquad_scan.hip)
+  ConvFft = 2,            // FFT convolver: forward transform, multiply-accumulate, inverse transform
+  ZeroFill = 3,           // memset of Step::zero_ptr
+  ConvDirect = 4,         // direct FIR (short impulse responses)
+  BiquadCoefs = 5,        // per-frame biquad coefficients from a-rate params
+  IirStream = 6,          // streaming IIR kernel
+  Delay = 7,              // delay gather (reader half of a DelayNode)
+  Loop = 8,               // feedback loop rendered quantum by quantum inside one launch (loop_kernel)
+  Osc = 9,                // oscillator
+  Dyn = 10,               // dynamic-count group (dyn_kernel)
+  ConvCodes = 11,         // per-quantum channel-count codes of a convolver's output
+  BiquadHp = 12,          // digest of a shared per-frame coefficient table
+  PannerGeom = 13,        // per-frame panner geometry
+  Timeline = 14,          // automation timelines replayed on the device
+  Link = 15,              // link table of a frozen-state node (waa_frozen.hip)
+  QGemm = 16,             // one resampling stage of an oversampled WaveShaper (qgemm_kernel)
+  Hrtf = 17,              // HRTF FIR
+  BiquadTileDigest = 18,  // tile digests of an a-rate biquad (waa_biquad_lanes.hip)
+  BiquadLanes = 19,       // a-rate biquad: pass A + chain + pass B (waa_biquad_lanes.hip)
+  OsFft = 20,             // the oversampled WaveShaper in one launch (waa_osfft.hip)
+  Compressor = 21,        // DynamicsCompressorNode: level, detector, apply (waa_compressor.hip)
+  Route = 22,             // channel routing (route_kernel)
+};
+constexpr int N_STEP_KINDS = 23;
+
+// The per-kind facts that the planner's loop handling, its fusions and the executor ask for, in one place.
+struct StepTraits {
+  const char* name;     // messages and the launch-list dump
+  bool once_in_loop;    // inside a feedback loop: depends only on data from outside it, runs once before the blocks (runs_once_in_loop)
+  bool quantum_ranged;  // can be launched over a range of render quanta: exactly the cases of run_step_q (waa_run.cpp)
+  bool frozen_state;    // launch of a frozen-state node: refused inside a block-scheduled loop
+  // the echo-tail fusion (waa_plan_loops.cpp) counts the readers of a delay line from step_io's read sets and leaves the whole plan
+  // alone when a launch is of a kind whose reads it takes as unknown.  ConvCodes and Link report none to step_io; Compressor and
+  // Route report theirs, but were added after the fusion and have not been tried with it.
+  bool reads_unknown_to_echo_fusion;
+};
+inline const StepTraits& step_traits(StepKind k) {
+  static const StepTraits traits[] = {
+      // name                 once   ranged frozen unknown
+      {"chain",               false, false, false, false},
+      {"biquad_stream",       false, false, false, false},
+      {"conv_fft",            false, true,  false, false},
+      {"zero_fill",           true,  false, false, false},
+      {"conv_direct",         false, false, false, false},
+      {"biquad_coefs",        true,  false, false, false},
+      {"iir_stream",          false, false, false, false},
+      {"delay",               false, false, false, false},
+      {"loop",                false, false, false, false},
+      {"osc",                 false, false, false, false},
+      {"dyn",                 false, true,  false, false},
+      {"conv_codes",          false, true,  false, true},
+      {"biquad_hp",           true,  false, false, false},
+      {"panner_geom",         true,  false, false, false},
+      {"timeline",            true,  false, false, false},
+      {"link",                false, true,  true,  true},
+      {"qgemm",               false, false, true,  false},
+      {"hrtf",                false, true,  true,  false},
+      {"biquad_tile_digest",  false, false, false, false},
+      {"biquad_lanes",        false, false, false, false},
+      {"os_fft",              false, true,  true,  false},
+      {"compressor",          false, false, false, true},
+      {"route",               false, false, false, true},
+  };
+  static_assert(sizeof traits / sizeof traits[0] == N_STEP_KINDS, "one row per StepKind, in the enum's order");
+  return traits[(int)k];
+}
+
 struct Step {
-  int kind = 0;  // 22 channel routing (route_kernel), 21 DynamicsCompressorNode (level, detector, apply: waa_compressor.hip), 15 link table of a frozen-state node, 16 one resampling stage of an oversampled WaveShaper (qgemm_kernel), 17 HRTF FIR; 0 chain (interpreter kernel), 1 streaming biquad kernel, 2 FFT convolver, 3 zero-fill, 4 direct FIR, 5 per-frame biquad coefficients, 6 streaming IIR kernel, 7 delay gather, 8 feedback loop, 9 oscillator, 10 dynamic-count group (dyn_kernel), 11 convolver codes, 12 digest of a shared per-frame coefficient table, 13 per-frame panner geometry, 14 automation timelines replayed on the device
+  StepKind kind = StepKind::Chain;
   ChainDesc chain{};
   BiquadStreamDesc bq{};
-  BiquadScanCtl scan{};   // kind 1 with scan.payload: the time-parallel form (waa_biquad_scan.hip)
-  BiquadLanesDesc lanes{};  // kinds 18 (tile digests) and 19 (pass A + chain + pass B), waa_biquad_lanes.hip
+  BiquadScanCtl scan{};   // BiquadStream with scan.payload: the time-parallel form (waa_biquad_scan.hip)
+  BiquadLanesDesc lanes{};  // BiquadTileDigest and BiquadLanes, waa_biquad_lanes.hip
   ConvDesc conv{};
   BiquadCoefDesc coef{};
   IirStreamDesc iir{};
@@ -264,10 +334,10 @@ struct Step {
   TimelineDesc tl{};
   LinkDesc link{};
   QGemmDesc qgemm{};
-  OsFftDesc osfft{};      // kind 20: the oversampled WaveShaper in one launch (waa_osfft.hip)
+  OsFftDesc osfft{};      // OsFft: the oversampled WaveShaper in one launch (waa_osfft.hip)
   HrtfDesc hrtf{};
-  RouteDesc route{};      // kind 22: ChannelMergerNode / the input bus of a ChannelSplitterNode (waa_route.hip; reads / writes in loop_reads / loop_writes)
-  CompDesc comp{};        // kind 21 (profile slots: slot_fwd = level, slot_mac = detector, slot_inv = apply)
+  RouteDesc route{};      // Route: ChannelMergerNode / the input bus of a ChannelSplitterNode (waa_route.hip; reads / writes in loop_reads / loop_writes)
+  CompDesc comp{};        // Compressor (profile slots: slot_fwd = level, slot_mac = detector, slot_inv = apply)
   int slot_fwd = -1, slot_mac = -1, slot_inv = -1;
   void* zero_ptr = nullptr;
   size_t zero_bytes = 0;
@@ -296,6 +366,12 @@ struct Step {
   bool echo_ff = false;
   ChainDesc echo_line{};
 };
+
+// A launch planned for a member of a feedback loop that depends only on data from outside the loop: it runs once, over the whole
+// render, in front of the blocks.  Param tables and fills by kind, and a chain that is nothing but an AudioParam's summing chain.
+inline bool runs_once_in_loop(const Step& st) {
+  return step_traits(st.kind).once_in_loop || (st.kind == StepKind::Chain && st.chain.n_ops == 1 && st.chain.ops[0].kind == OP_PARAM_ADD);
+}
 
 struct SchedOut {
   std::vector<QRec> qrec;
@@ -568,6 +644,8 @@ std::vector<float> param_per_quantum(const waa_batch* b, const ParamStore& p, ui
 
 // ---- waa_plan.cpp: graph -> launch plan -----------------------------------------------------------------
 int build_plan(waa_batch* b);
+// waa_run.cpp: the launches of the current plan, from the initial state
+int run_steps(waa_batch* b);
 // waa_frozen_host.cpp: WaveShaper 2x / 4x and the HRTF panner as node-major steps; src_id >= 0: static plan, the node's
 // only input is that source node (its host-known codes stand in for the codes a dynamic plan computes on the device)
 int plan_oversampler(waa_batch* b, uint32_t id, int src_id);

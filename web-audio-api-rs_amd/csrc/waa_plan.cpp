@@ -41,7 +41,7 @@ int device_timeline_param(waa_batch* b, const ParamStore& p, ParamRef* ref) {
     h.defv = p.defv;
   }
   Step st;
-  st.kind = 14;
+  st.kind = StepKind::Timeline;
   TimelineDesc& d = st.tl;
   std::memset(&d, 0, sizeof d);
   TlHeader* d_hdr = nullptr;
@@ -738,7 +738,7 @@ int emit_segments(waa_batch* b, std::vector<InputRef> inputs, int in_nch, int in
     }
     if (o.kind == OP_IIR) {
       Step st;
-      st.kind = 6;
+      st.kind = StepKind::IirStream;
       IirStreamDesc& q = st.iir;
       std::memset(&q, 0, sizeof q);
       q.in = inputs[0];
@@ -810,11 +810,11 @@ int emit_segments(waa_batch* b, std::vector<InputRef> inputs, int in_nch, int in
       L.tile1 = b->n_tiles;
       L.fast_tiles = inputs[0].kind == IN_SOURCE ? inputs[0].fast_tiles
                                                  : (inputs[0].valid ? (uint32_t)std::min<uint64_t>(inputs[0].valid / TILE, b->n_tiles) : b->n_tiles);
-      dstep.kind = 18;
+      dstep.kind = StepKind::BiquadTileDigest;
       dstep.lanes = L;
       dstep.profile_slot = slot_for(b, "biquad_tile_digest_kernel");
       Step ls;
-      ls.kind = 19;
+      ls.kind = StepKind::BiquadLanes;
       ls.lanes = L;
       ls.profile_slot = slot_for(b, "biquad_lanes_kernel");
       b->steps.push_back(ls);
@@ -831,7 +831,7 @@ int emit_segments(waa_batch* b, std::vector<InputRef> inputs, int in_nch, int in
       continue;
     }
     Step st;
-    st.kind = 1;
+    st.kind = StepKind::BiquadStream;
     BiquadStreamDesc& q = st.bq;
     std::memset(&q, 0, sizeof q);
     q.in = inputs[0];
@@ -1119,6 +1119,22 @@ void compute_order(const waa_batch* b, std::vector<uint8_t>* cut_out, std::vecto
       if (!muted[*it & ~VTX_READER]) items.push_back(*it);
     *cut_out = c.cut;
   }
+}
+
+// Throw the plan so far away and plan the graph again (the caller has set the flag that makes the second pass differ:
+// force_dynamic, no_short_ring).  Device allocations stay with the batch.
+static int restart_plan(waa_batch* b) {
+  b->steps.clear();
+  b->group_tiles.clear();
+  b->qgroup_quanta.clear();
+  b->state_bufs.clear();
+  b->plan_log.clear();
+  for (auto& nd : b->nodes) {
+    nd.sig = SignalRef{};
+    nd.hist = SignalRef{};
+    nd.hist_is_temp = false;
+  }
+  return build_plan_impl(b);
 }
 
 static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vector<uint8_t>& muted) {
@@ -2261,17 +2277,7 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
           // the static loop kernel covers Gain / Biquad / WaveShaper / k-rate StereoPanner / Delay members only; the
           // dynamic-count kernel renders every node kind quantum by quantum (waa_dyn.hip): plan the graph again with it
           b->force_dynamic = true;
-          b->steps.clear();
-          b->group_tiles.clear();
-          b->qgroup_quanta.clear();
-          b->state_bufs.clear();
-          b->plan_log.clear();
-          for (auto& nd : b->nodes) {
-            nd.sig = SignalRef{};
-            nd.hist = SignalRef{};
-            nd.hist_is_temp = false;
-          }
-          return build_plan_impl(b);
+          return restart_plan(b);
         }
         if (e) return e;
         continue;
@@ -2297,8 +2303,8 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
         Step& st = b->steps[k];
         st.group = group;
         // steps that only depend on data from outside the loop run once, over the full range, before the blocks
-        st.prologue = st.kind == 5 || st.kind == 12 || st.kind == 13 || st.kind == 14 || st.kind == 3 || (st.kind == 0 && st.chain.n_ops == 1 && st.chain.ops[0].kind == OP_PARAM_ADD);
-        if (st.prologue && st.kind == 0) {
+        st.prologue = runs_once_in_loop(st);
+        if (st.prologue && st.kind == StepKind::Chain) {
           // ... unless the param is modulated from INSIDE the loop: its summing chain then reads what a launch of this
           // group writes and belongs to the blocks, in its place in the order
           const StepIo io = step_io(b, st);
@@ -2309,8 +2315,8 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
               if (std::find(w.writes.begin(), w.writes.end(), r) != w.writes.end()) st.prologue = false;
           }
         }
-        st.prologue |= st.kind == 18;
-        if (st.kind == 15 || st.kind == 16 || st.kind == 17 || st.kind == 20)
+        st.prologue |= st.kind == StepKind::BiquadTileDigest;  // (this path only: a quantum-blocked loop has no use for it)
+        if (step_traits(st.kind).frozen_state)
           return fail(WAA_ERR_OUT_OF_SCOPE, "this node kind cannot be rendered inside a feedback loop");
       }
       plan_note(b, "feedback loop: block-scheduled, %u tile(s) = %u frames per block, %zu step(s) per block", bt, bt * TILE,
@@ -2340,7 +2346,7 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
               }
           }
         };
-        if (n_body == 1 && b->steps[body].kind == 0 && !measure_switch("WAA_NO_ECHO_RING")) {
+        if (n_body == 1 && b->steps[body].kind == StepKind::Chain && !measure_switch("WAA_NO_ECHO_RING")) {
           delay_range();
           ChainDesc cd = b->steps[body].chain;
           cd.tile0 = 0;
@@ -2357,7 +2363,7 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
           }
         }
         // delayed read -> streaming biquad (constant coefficients) -> sum into the line: the filtered echo, the ring kernel's BQ form
-        if (n_body == 3 && b->steps[bodies[0]].kind == 0 && b->steps[bodies[1]].kind == 1 && b->steps[bodies[2]].kind == 0 &&
+        if (n_body == 3 && b->steps[bodies[0]].kind == StepKind::Chain && b->steps[bodies[1]].kind == StepKind::BiquadStream && b->steps[bodies[2]].kind == StepKind::Chain &&
             !b->steps[bodies[1]].scan.payload && !measure_switch("WAA_NO_ECHO_RING") && !measure_switch("WAA_NO_ECHO_BQ")) {
           delay_range();
           Step &rd = b->steps[bodies[0]], &fl = b->steps[bodies[1]], &sm = b->steps[bodies[2]];
@@ -2394,17 +2400,7 @@ static int build_plan_rest(waa_batch* b, std::vector<uint32_t>& items, std::vect
         for (size_t k : bodies) qualified |= b->steps[k].echo_fb >= 0;
         if (short_ring && !qualified) {
           b->no_short_ring = true;
-          b->steps.clear();
-          b->group_tiles.clear();
-          b->qgroup_quanta.clear();
-          b->state_bufs.clear();
-          b->plan_log.clear();
-          for (auto& nd : b->nodes) {
-            nd.sig = SignalRef{};
-            nd.hist = SignalRef{};
-            nd.hist_is_temp = false;
-          }
-          return build_plan_impl(b);
+          return restart_plan(b);
         }
         if (short_ring) plan_note(b, "  (a feedback delay shorter than a tile: the ring kernel walks it in chunks shorter than the delay)");
       }

@@ -38,8 +38,8 @@ StepIo step_io(const waa_batch* b, const Step& st) {
 }
 static StepIo step_io_raw(const Step& st) {
   StepIo io;
-  switch (st.kind) {
-    case 0: {
+  switch (st.kind) {  // (every kind, no default: a new kind that forgets its case is a compiler warning, not an empty read set)
+    case StepKind::Chain: {
       const ChainDesc& c = st.chain;
       for (int k = 0; k < c.n_inputs; k++) io_input(c.in[k], io);
       for (int o = 0; o < c.n_ops; o++) {
@@ -54,35 +54,35 @@ static StepIo step_io_raw(const Step& st) {
       io.writes.push_back(c.out.base);
       break;
     }
-    case 1:
+    case StepKind::BiquadStream:
       io_input(st.bq.in, io);
       if (st.bq.vary >= 2) io.reads.push_back(st.bq.coefs);
       if (st.bq.vary == 3) io.reads.push_back(st.bq.hp);
       io.writes.push_back(st.bq.out.base);
       break;
-    case 2:
-    case 4:
+    case StepKind::ConvFft:
+    case StepKind::ConvDirect:
       io.reads.push_back(st.conv.in.base);
       io.writes.push_back(st.conv.out.base);
       break;
-    case 21:
+    case StepKind::Compressor:
       io.reads.push_back(st.comp.in.base);
       io.writes.push_back(st.comp.out.base);
       break;
-    case 3:
+    case StepKind::ZeroFill:
       io.writes.push_back(st.zero_ptr);
       break;
-    case 5:
+    case StepKind::BiquadCoefs:
       io_param(st.coef.frequency, io);
       io_param(st.coef.detune, io);
       io_param(st.coef.q, io);
       io_param(st.coef.gain, io);
       io.writes.push_back(st.coef.coefs);
       break;
-    case 14:
+    case StepKind::Timeline:
       io.writes.push_back(st.tl.out);
       break;
-    case 13:
+    case StepKind::PannerGeom:
       for (int k = 0; k < 15; k++) io_param(st.geom.p[k], io);
       io.writes.push_back(st.geom.az);
       io.writes.push_back(st.geom.gl_mono);
@@ -92,47 +92,51 @@ static StepIo step_io_raw(const Step& st) {
       io.writes.push_back(st.geom.dg);
       io.writes.push_back(st.geom.cg);
       break;
-    case 12:
+    case StepKind::BiquadHp:
       if (st.hp.coefs) {
         io.reads.push_back(st.hp.coefs);
         io.writes.push_back(st.hp.hp);
       }
       break;
-    case 18:
+    case StepKind::BiquadTileDigest:
       io.reads.push_back(st.lanes.coefs);
       io.writes.push_back(st.lanes.ht);
       break;
-    case 19:
+    case StepKind::BiquadLanes:
       io_input(st.lanes.in, io);
       io.reads.push_back(st.lanes.coefs);
       io.reads.push_back(st.lanes.ht);
       io.writes.push_back(st.lanes.out.base);
       break;
-    case 6:
+    case StepKind::IirStream:
       io_input(st.iir.in, io);
       io.writes.push_back(st.iir.out.base);
       break;
-    case 7:
+    case StepKind::Delay:
       io.reads.push_back(st.delay.in.base);
       io_param(st.delay.delay, io);
       io.writes.push_back(st.delay.out.base);
       io.feedback_reader = st.delay.in_cycle != 0;
       break;
-    case 22:  // (the terms of a route launch: recorded by the planner, views resolved)
-    case 8:
-    case 10:
-    case 16:
-    case 17:
-    case 20:
+    case StepKind::Route:  // (the terms of a route launch: recorded by the planner, views resolved)
+    case StepKind::Loop:
+    case StepKind::Dyn:
+    case StepKind::QGemm:
+    case StepKind::Hrtf:
+    case StepKind::OsFft:
       io.reads = st.loop_reads;
       io.writes = st.loop_writes;
       break;
-    case 9:
+    case StepKind::Osc:
       io_param(st.osc.frequency, io);
       io_param(st.osc.detune, io);
       io.writes.push_back(st.osc.out.base);
       break;
-    default:
+    case StepKind::ConvCodes:
+    case StepKind::Link:
+      // nothing reported: both work on per-quantum code tables and state words, which no launch list entry orders.  ConvCodes also
+      // tests the convolver's input and clears quanta of its output in place; it is planned right behind the ConvFft launch that
+      // reports both signals.  (This is why the echo-tail fusion takes their reads as unknown: StepTraits.)
       break;
   }
   return io;
@@ -148,14 +152,15 @@ int validate_plan(waa_batch* b) {
   }
   for (size_t k = 0; k < b->steps.size(); k++) {
     const StepIo& io = ios[k];
-    if (b->steps[k].kind == 8 || b->steps[k].kind == 10) {  // the items of a quantum-serial launch hand over inside the kernel
+    const StepKind kind = b->steps[k].kind;
+    if (kind == StepKind::Loop || kind == StepKind::Dyn) {  // the items of a quantum-serial launch hand over inside the kernel
       for (const void* w : io.writes) written.insert(w);
     }
     for (const void* r : io.reads) {
       if (!r || !produced.count(r) || written.count(r)) continue;
       if (io.feedback_reader && r == b->steps[k].delay.in.base) continue;
-      return fail(WAA_ERR_INVALID_STATE, "internal: launch %zu of the plan (kind %d) reads a buffer that a later launch produces", k,
-                  b->steps[k].kind);
+      return fail(WAA_ERR_INVALID_STATE, "internal: launch %zu of the plan (kind %d, %s) reads a buffer that a later launch produces", k,
+                  (int)kind, step_traits(kind).name);
     }
     for (const void* w : io.writes)
       if (w) written.insert(w);

@@ -79,7 +79,7 @@ int plan_compressor(waa_batch* b, uint32_t id) {
   float* xl = nullptr;
   if ((e = dev_alloc(b, &xl, (size_t)b->n_inst * b->lp))) return e;
   Step st;
-  st.kind = 21;
+  st.kind = StepKind::Compressor;
   CompDesc& d = st.comp;
   std::memset(&d, 0, sizeof d);
   d.in = in_sig;

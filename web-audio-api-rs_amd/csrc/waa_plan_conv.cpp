@@ -150,13 +150,13 @@ int plan_convolver(waa_batch* b, uint32_t id) {
   // batch is one launch; every channel of every instance still drops what lies behind its own trim, below)
   const uint64_t len = lti ? n.ir_lti_len /* (already cut where the folded response ends) */ : conv_longest_trim(b, n);
   Step st;
-  st.kind = 2;
+  st.kind = StepKind::ConvFft;
   ConvDesc& cv = st.conv;
   std::memset(&cv, 0, sizeof cv);
   if (len == 0) {
     // all-zero impulse response: FFTConvolver::process outputs zeros
     Step z;
-    z.kind = 3;
+    z.kind = StepKind::ZeroFill;
     z.zero_ptr = n.sig.base;
     z.zero_bytes = (size_t)b->n_inst * n.out_nch * b->lp * sizeof(float);
     b->steps.push_back(z);
@@ -242,7 +242,7 @@ int plan_convolver(waa_batch* b, uint32_t id) {
   if (e) return e;
   cv.ir = d_ir;
   if (direct_fir) {
-    st.kind = 4;
+    st.kind = StepKind::ConvDirect;
     st.slot_mac = slot_for(b, per_inst ? "conv_inst_direct_kernel" : "conv_direct_kernel");
     b->steps.push_back(st);
     plan_note(b, "convolver node %u: direct FIR taps=%llu cin=%d cout=%d terms=%d%s", id, (unsigned long long)len, cv.cin,
@@ -299,7 +299,7 @@ int plan_convolver(waa_batch* b, uint32_t id) {
           if (cv.terms[t].out_ch == co && conv_trimmed(n.ir_of(inst, cv.terms[t].ir_ch), n.ir_len) > 0) silent = false;
         if (!silent) continue;
         Step z;
-        z.kind = 3;
+        z.kind = StepKind::ZeroFill;
         z.zero_ptr = n.sig.base + (uint64_t)inst * n.sig.inst_stride + (uint64_t)co * n.sig.ch_stride;
         z.zero_bytes = (size_t)b->lp * sizeof(float);
         b->steps.push_back(z);

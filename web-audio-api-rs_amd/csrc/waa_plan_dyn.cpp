@@ -94,7 +94,7 @@ int plan_dynamic_groups(waa_batch* b, const DynPlanCtx& c) {
     }
     std::vector<DynItem> host(pending.size());
     Step st;
-    st.kind = 10;
+    st.kind = StepKind::Dyn;
     std::string desc;
     for (size_t k = 0; k < pending.size(); k++) {
       const uint32_t v = pending[k], id = v & ~VTX_READER;
@@ -450,7 +450,7 @@ int plan_dynamic_groups(waa_batch* b, const DynPlanCtx& c) {
     if (e) return e;
     if ((e = alloc_codes(&n.code))) return e;
     Step cst;
-    cst.kind = 11;
+    cst.kind = StepKind::ConvCodes;
     ConvCodeDesc& cd = cst.ccode;
     std::memset(&cd, 0, sizeof cd);
     cd.in_code = in_code;
@@ -634,17 +634,18 @@ int plan_dynamic_groups(waa_batch* b, const DynPlanCtx& c) {
           if (e) return e;
           for (size_t k2 = first; k2 < b->steps.size(); k2++) {
             Step& fs = b->steps[k2];
-            if (fs.kind != 15 && fs.kind != 17 && fs.kind != 20 && fs.kind != 2 && fs.kind != 11)
-              return fail(WAA_ERR_OUT_OF_SCOPE, "node %u inside a feedback loop: this form of the node has no ranged launch (step kind %d)", vid, fs.kind);
-            if (fs.kind == 2 && fs.conv.block != RQ)
+            // (a cut node plans no dyn_kernel group of its own: the one ranged kind that is refused here)
+            if (!step_traits(fs.kind).quantum_ranged || fs.kind == StepKind::Dyn)
+              return fail(WAA_ERR_OUT_OF_SCOPE, "node %u inside a feedback loop: this form of the node has no ranged launch (step kind %d)", vid, (int)fs.kind);
+            if (fs.kind == StepKind::ConvFft && fs.conv.block != RQ)
               return fail(WAA_ERR_OUT_OF_SCOPE, "a ConvolverNode inside a feedback loop is out of scope (node %u: %d-frame partitions)", vid, fs.conv.block);
             fs.qgroup = cur_qgroup;
-            if (fs.kind == 15 || fs.kind == 11) {
+            if (fs.kind == StepKind::Link || fs.kind == StepKind::ConvCodes) {
               int32_t* lst = nullptr;
-              const size_t ints = fs.kind == 11 ? (size_t)CONV_CODE_STATE_INTS : 4;
+              const size_t ints = fs.kind == StepKind::ConvCodes ? (size_t)CONV_CODE_STATE_INTS : 4;
               if ((e = dev_alloc(b, &lst, (size_t)b->n_inst * ints))) return e;
               b->state_bufs.push_back({lst, (size_t)b->n_inst * ints * sizeof(int32_t)});
-              (fs.kind == 15 ? fs.link.state : fs.ccode.state) = lst;
+              (fs.kind == StepKind::Link ? fs.link.state : fs.ccode.state) = lst;
             }
           }
         }
@@ -657,13 +658,11 @@ int plan_dynamic_groups(waa_batch* b, const DynPlanCtx& c) {
       size_t n_ranged = 0;
       for (size_t k2 = first_loop_step; k2 < b->steps.size(); k2++) {
         Step& ls = b->steps[k2];
-        const bool ranged = ls.kind == 10 || ls.kind == 15 || ls.kind == 17 || ls.kind == 20 || ls.kind == 2 || ls.kind == 11;
+        const bool ranged = step_traits(ls.kind).quantum_ranged;
         if (ranged && ls.qgroup != cur_qgroup) return fail(WAA_ERR_INVALID_STATE, "internal: ranged launch outside its loop");
         if (!ranged) {
-          const bool once = ls.kind == 5 || ls.kind == 12 || ls.kind == 13 || ls.kind == 14 || ls.kind == 3 ||
-                            (ls.kind == 0 && ls.chain.n_ops == 1 && ls.chain.ops[0].kind == OP_PARAM_ADD);
-          if (!once)
-            return fail(WAA_ERR_OUT_OF_SCOPE, "a feedback loop with a frozen-state node inside needs a launch of kind %d per block: out of scope", ls.kind);
+          if (!runs_once_in_loop(ls))
+            return fail(WAA_ERR_OUT_OF_SCOPE, "a feedback loop with a frozen-state node inside needs a launch of kind %d per block: out of scope", (int)ls.kind);
           ls.qgroup = cur_qgroup;
           ls.prologue = true;
         }

@@ -10,6 +10,18 @@
 namespace waa {
 namespace host {
 
+// Does the launch read the delay line `line`: through its read set `io`, or through a delayed input of one of the kinds that
+// gather from a delay line themselves (a delayed read marked `feedback` is left out of the read sets: the validation's legal
+// read-before-write)?
+static bool reads_line(const Step& st, const StepIo& io, const void* line) {
+  auto delayed_from = [&](const InputRef& in) { return in.kind == IN_DELAYED && in.sig.base == line; };
+  bool reads = std::find(io.reads.begin(), io.reads.end(), line) != io.reads.end();
+  if (st.kind == StepKind::Chain)
+    for (int q = 0; q < st.chain.n_inputs; q++) reads |= delayed_from(st.chain.in[q]);
+  return reads || (st.kind == StepKind::BiquadStream && delayed_from(st.bq.in)) || (st.kind == StepKind::IirStream && delayed_from(st.iir.in)) ||
+         (st.kind == StepKind::BiquadLanes && delayed_from(st.lanes.in));
+}
+
 // An echo loop rendered by the LDS-ring kernel (Step::echo_fb): when the line it writes has exactly ONE reader in the whole plan
 // and that reader is a plain sum of the delayed line and of signals the loop step reads too (the destination's  dry + wet),
 // the ring kernel renders that sum as well and the line is never stored (waa_echo.hip, "the tail").  Decided on the finished
@@ -30,12 +42,7 @@ static void fuse_filtered_echo_tail(waa_batch* b, size_t l) {
     const Step& sk = b->steps[k];
     if (sk.echo_fused && sk.group == ls.group) continue;  // (the delayed read and the filter: inside the launch)
     const StepIo io = step_io(b, sk);
-    auto delayed_from = [&](const InputRef& in) { return in.kind == IN_DELAYED && in.sig.base == line; };
-    bool rl = std::find(io.reads.begin(), io.reads.end(), line) != io.reads.end();
-    if (sk.kind == 0)
-      for (int q = 0; q < sk.chain.n_inputs; q++) rl |= delayed_from(sk.chain.in[q]);
-    rl |= (sk.kind == 1 && delayed_from(sk.bq.in)) || (sk.kind == 6 && delayed_from(sk.iir.in)) || (sk.kind == 19 && delayed_from(sk.lanes.in));
-    line_readers += rl ? 1 : 0;
+    line_readers += reads_line(sk, io, line) ? 1 : 0;
     if (std::find(io.reads.begin(), io.reads.end(), y) != io.reads.end()) {
       y_readers++;
       reader = k;
@@ -56,7 +63,7 @@ static void fuse_filtered_echo_tail(waa_batch* b, size_t l) {
     Step& ts = b->steps[reader];
     EchoTail t{};
     const char* why = "it is not an element-wise launch";
-    if (ts.kind == 0 && ts.group < 0 && echo_tail_applicable(ls.chain, ls.echo_fb, ts.chain, &t, &why, &ls.echo_bq)) {
+    if (ts.kind == StepKind::Chain && ts.group < 0 && echo_tail_applicable(ls.chain, ls.echo_fb, ts.chain, &t, &why, &ls.echo_bq)) {
       t.store_line = ls.echo_bq.store_line;
       ls.echo_tail = t;
       ls.echo_tail_step = (int)reader;
@@ -75,10 +82,10 @@ static void fuse_filtered_echo_tail(waa_batch* b, size_t l) {
 void fuse_echo_tails(waa_batch* b) {
   if (measure_switch("WAA_NO_ECHO_TAIL")) return;
   for (const Step& st : b->steps)
-    if (st.kind == 11 || st.kind == 15 || st.kind > 20) return;
+    if (step_traits(st.kind).reads_unknown_to_echo_fusion) return;
   for (size_t l = 0; l < b->steps.size(); l++) {
     Step& ls = b->steps[l];
-    if (ls.kind != 0 || ls.echo_fb < 0) continue;
+    if (ls.kind != StepKind::Chain || ls.echo_fb < 0) continue;
     if (ls.echo_bq.coefs) {
       fuse_filtered_echo_tail(b, l);
       continue;
@@ -91,14 +98,7 @@ void fuse_echo_tails(waa_batch* b) {
       if (k == l) continue;
       const Step& sk = b->steps[k];
       const StepIo io = step_io(b, sk);
-      // (a delayed read marked `feedback` is left out of the read sets: the validation's legal read-before-write)
-      auto delayed_from = [&](const InputRef& in) { return in.kind == IN_DELAYED && in.sig.base == line; };
-      bool reads = std::find(io.reads.begin(), io.reads.end(), line) != io.reads.end();
-      if (sk.kind == 0)
-        for (int q = 0; q < sk.chain.n_inputs; q++) reads |= delayed_from(sk.chain.in[q]);
-      reads |= (sk.kind == 1 && delayed_from(sk.bq.in)) || (sk.kind == 6 && delayed_from(sk.iir.in)) ||
-               (sk.kind == 19 && delayed_from(sk.lanes.in));
-      if (reads) {
+      if (reads_line(sk, io, line)) {
         n_readers++;
         reader = k;
       }
@@ -125,7 +125,7 @@ void fuse_echo_tails(waa_batch* b) {
     Step& ts = b->steps[reader];
     EchoTail t{};
     const char* why = "it is not an element-wise launch";
-    if (ts.kind != 0 || ts.group >= 0 || !echo_tail_applicable(ls.chain, ls.echo_fb, ts.chain, &t, &why)) {
+    if (ts.kind != StepKind::Chain || ts.group >= 0 || !echo_tail_applicable(ls.chain, ls.echo_fb, ts.chain, &t, &why)) {
       plan_note(b, "echo loop: launch %zu, the only reader of the delay line, is not a plain sum of the delayed line and of the loop's inputs (%s): the line is stored", reader, why);
       continue;
     }
@@ -148,7 +148,7 @@ void ring_feed_forward_echoes(waa_batch* b) {
   if (b->n_inst < (uint32_t)(mi ? atoi(mi) : 256)) return;
   for (size_t k = 0; k < b->steps.size(); k++) {
     Step& st = b->steps[k];
-    if (st.kind != 0 || st.group >= 0 || st.echo_fused || st.chain.n_ops != 0) continue;
+    if (st.kind != StepKind::Chain || st.group >= 0 || st.echo_fused || st.chain.n_ops != 0) continue;
     bool any = false;
     for (int q = 0; q < st.chain.n_inputs; q++) any |= st.chain.in[q].kind == IN_DELAYED;
     if (!any) continue;
@@ -215,7 +215,7 @@ int plan_folded_delay_line(waa_batch* b, uint32_t id) {
 int plan_delay_reader(waa_batch* b, uint32_t id) {
   Node& n = b->nodes[id];
   Step st;
-  st.kind = 7;
+  st.kind = StepKind::Delay;
   DelayDesc& d = st.delay;
   std::memset(&d, 0, sizeof d);
   const bool in_cycle = id < b->cut.size() && b->cut[id];
@@ -433,7 +433,7 @@ int plan_loop(waa_batch* b, const std::vector<uint32_t>& loop_items) {
   int e = dev_upload(b, &dev, host);
   if (e) return e;
   Step st;
-  st.kind = 8;
+  st.kind = StepKind::Loop;
   LoopDesc& d = st.loop;
   std::memset(&d, 0, sizeof d);
   d.items = dev;

@@ -52,7 +52,7 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
         // a-rate params: coefficients per frame (biquad_filter.rs:837-855), computed on the device in f64 from
         // the per-frame param values into a table the chain kernel streams
         Step cs;
-        cs.kind = 5;
+        cs.kind = StepKind::BiquadCoefs;
         BiquadCoefDesc& cdsc = cs.coef;
         std::memset(&cdsc, 0, sizeof cdsc);
         int e;
@@ -88,7 +88,7 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
         o.i1 = (int32_t)b->steps.size() - 1;  // the coefficient step: emit_segments may switch it to the lane-major layout
         {
           Step hs;  // placeholder for the digest of a shared table (a no-op unless emit_segments fills it in)
-          hs.kind = 12;
+          hs.kind = StepKind::BiquadHp;
           std::memset(&hs.hp, 0, sizeof hs.hp);
           hs.profile_slot = slot_for(b, "biquad_hp_kernel");
           b->steps.push_back(hs);
@@ -272,7 +272,7 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
         // the device (waa_panner.hip).  Quanta in which all nine listener params happen to be single-valued keep the
         // once-per-quantum rule (first value of every param), flagged per quantum from the value blocks.
         Step gs;
-        gs.kind = 13;
+        gs.kind = StepKind::PannerGeom;
         PannerGeomDesc& g = gs.geom;
         std::memset(&g, 0, sizeof g);
         bool shared = true;

@@ -69,7 +69,7 @@ int push_route_step(waa_batch* b, const std::vector<std::vector<RouteTerm>>& row
   std::vector<RouteTerm> terms;
   std::vector<uint32_t> row_off{0u};
   Step st;
-  st.kind = 22;
+  st.kind = StepKind::Route;
   for (const auto& r : rows) {
     for (const RouteTerm& t : r) {
       terms.push_back(t);

@@ -302,7 +302,7 @@ int plan_oscillator(waa_batch* b, uint32_t id) {
   const bool check_replay = measure_switch("WAA_OSC_PLAN_CHECK") != nullptr;
   Node& n = b->nodes[id];
   Step st;
-  st.kind = 9;
+  st.kind = StepKind::Osc;
   OscDesc& d = st.osc;
   std::memset(&d, 0, sizeof d);
   int e;
@@ -521,12 +521,12 @@ void fuse_fm_operators(waa_batch* b) {
   if (measure_switch("WAA_NO_FM_FOLD")) return;
   for (size_t c = 0; c < b->steps.size(); c++) {
     Step& cs = b->steps[c];
-    if (cs.kind != 9 || !cs.osc.active || cs.osc.frequency.mode != 2 || cs.osc.fm_q || cs.group >= 0) continue;
+    if (cs.kind != StepKind::Osc || !cs.osc.active || cs.osc.frequency.mode != 2 || cs.osc.fm_q || cs.group >= 0) continue;
     const void* table = cs.osc.frequency.base;
     int pi = -1, mi = -1;
     for (size_t k = 0; k < c; k++) {
       const Step& st = b->steps[k];
-      if (st.kind == 0 && st.group < 0 && !st.echo_fused && (const void*)st.chain.out.base == table) pi = (int)k;
+      if (st.kind == StepKind::Chain && st.group < 0 && !st.echo_fused && (const void*)st.chain.out.base == table) pi = (int)k;
     }
     if (pi < 0) continue;
     Step& ps = b->steps[(size_t)pi];
@@ -537,7 +537,7 @@ void fuse_fm_operators(waa_batch* b) {
       continue;
     for (size_t k = 0; k < (size_t)pi; k++) {
       const Step& st = b->steps[k];
-      if (st.kind == 9 && st.group < 0 && !st.echo_fused && st.osc.table_q && st.osc.out.base == ch.in[0].sig.base) mi = (int)k;
+      if (st.kind == StepKind::Osc && st.group < 0 && !st.echo_fused && st.osc.table_q && st.osc.out.base == ch.in[0].sig.base) mi = (int)k;
     }
     if (mi < 0) continue;
     Step& ms = b->steps[(size_t)mi];
@@ -586,7 +586,7 @@ void fuse_lfo_params(waa_batch* b) {
   if (measure_switch("WAA_NO_LFO_FOLD")) return;
   for (size_t pi = 0; pi < b->steps.size(); pi++) {
     Step& ps = b->steps[pi];
-    if (ps.kind != 0 || ps.group >= 0 || ps.echo_fused) continue;
+    if (ps.kind != StepKind::Chain || ps.group >= 0 || ps.echo_fused) continue;
     const ChainDesc& ch = ps.chain;
     if (ch.n_ops != 1 || ch.ops[0].kind != OP_PARAM_ADD || ch.n_inputs != 1 || ch.in_nch != 1 || ch.in[0].kind != IN_SIGNAL ||
         ch.in[0].nch != 1 || ch.out.nch != 1 || ch.ops[0].p0.mode > 1 || (ch.in[0].has_gain && ch.in[0].gain.mode != 0) ||
@@ -595,7 +595,7 @@ void fuse_lfo_params(waa_batch* b) {
     int mi = -1;
     for (size_t k = 0; k < pi; k++) {
       const Step& st = b->steps[k];
-      if (st.kind == 9 && st.group < 0 && !st.echo_fused && st.osc.table_q && !st.osc.pa_on && st.osc.out.base == ch.in[0].sig.base) mi = (int)k;
+      if (st.kind == StepKind::Osc && st.group < 0 && !st.echo_fused && st.osc.table_q && !st.osc.pa_on && st.osc.out.base == ch.in[0].sig.base) mi = (int)k;
     }
     if (mi < 0) continue;
     Step& ms = b->steps[(size_t)mi];
