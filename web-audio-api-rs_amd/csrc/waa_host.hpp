@@ -429,6 +429,9 @@ struct waa_batch {
   // host copies of the per-instance source tables handed to the kernels (key: the device table): a signal wider than six channels is
   // rendered in channel slices (push_chain_step), and a slice of a SOURCE is the same table with its base pointers moved on
   std::map<const waa::SrcInst*, std::vector<waa::SrcInst>> src_tables;
+#ifdef WAA_MEASURE
+  std::map<uint32_t, const waa::SrcInst*> src_table_of_node;  // source node -> key of its table above (waa_debug_source_records)
+#endif
   std::vector<std::pair<void*, size_t>> ones_bufs;   // filled with 0xFF bytes at the start of every render
   std::vector<Step> steps;
   bool planned = false;

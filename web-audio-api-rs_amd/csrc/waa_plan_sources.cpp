@@ -217,6 +217,9 @@ int prepare_source_input(waa_batch* b, uint32_t id, InputRef* in) {
   in->src = d_insts;
   in->sched = d_scheds;
   b->src_tables[d_insts] = insts;
+#ifdef WAA_MEASURE
+  b->src_table_of_node[id] = d_insts;
+#endif
   in->fast_tiles = b->n_tiles;
   for (auto& si : insts) in->fast_tiles = std::min(in->fast_tiles, !si.base ? 0u : (si.linear_all ? b->n_tiles : si.fast_prefix));
   plan_note(b, "source node %u: %zu distinct schedule(s) for %u instance(s)", id, scheds.size(), b->n_inst);

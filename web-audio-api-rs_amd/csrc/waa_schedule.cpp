@@ -178,6 +178,42 @@ extern "C" uint64_t waa_debug_sched_verify(uint64_t* checked) {
   if (checked) *checked = g_sched_checked.load();
   return g_sched_mismatches.load();
 }
+#ifdef WAA_MEASURE
+// (measurement build, plan-only batches: the record tables the plan uploaded for `instance` of source node `node` — there they
+// lie in host memory, found through b->src_tables — as the readers see them; tests/test_source_schedules.py evaluates them in
+// numpy against the oracle's samples.  mode[n_quanta]; prev / next / k[n_quanta * 128]: slow quanta carry their records, fast
+// quanta prev = start + i (not wrapped, not cut at the buffer's end: the readers do both), silent quanta prev = -1.)
+extern "C" waa_status waa_debug_source_records(waa_batch* b, uint32_t node, uint32_t instance, uint32_t* mode, int64_t* prev, int64_t* next,
+                                               double* k) {
+  if (!b || !mode || !prev || !next || !k) return fail(WAA_ERR_INVALID_ARGUMENT, "null argument");
+  if (!b->dry) return fail(WAA_ERR_INVALID_STATE, "waa_debug_source_records: only plan-only batches keep their tables in host memory");
+  if (!b->planned) return fail(WAA_ERR_INVALID_STATE, "waa_debug_source_records: the batch has no plan yet");
+  if (instance >= b->n_inst) return fail(WAA_ERR_INVALID_ARGUMENT, "instance %u of %u", instance, b->n_inst);
+  auto of = b->src_table_of_node.find(node);
+  if (of == b->src_table_of_node.end()) return fail(WAA_ERR_INVALID_ARGUMENT, "node %u has no source table in this plan", node);
+  auto it = b->src_tables.find(of->second);
+  if (it == b->src_tables.end()) return fail(WAA_ERR_INVALID_STATE, "internal: a source table without its host copy");
+  const SrcSchedule& sc = it->second[instance].sc;
+  for (uint32_t q = 0; q < b->n_quanta; q++) {
+    const QRec r = sc.qrec[q];
+    mode[q] = r.mode;
+    for (int i = 0; i < RQ; i++) {
+      const size_t f = (size_t)q * RQ + i;
+      prev[f] = next[f] = -1;
+      k[f] = 0.;
+      if (r.mode == Q_SLOW) {
+        if (!sc.slow) return fail(WAA_ERR_INVALID_STATE, "internal: a slow quantum without a slow table");
+        prev[f] = sc.slow[f].prev;
+        next[f] = sc.slow[f].next;
+        k[f] = sc.slow[f].k;
+      } else if (r.mode == Q_FAST || r.mode == Q_FAST_LOOP) {
+        prev[f] = r.start + i;
+      }
+    }
+  }
+  return WAA_OK;
+}
+#endif
 
 void schedule_source(const waa_batch* b, const SourceSched& cfg, uint64_t frames, float buf_sr, bool has_buffer,
                      const std::vector<float>& rate_q, const std::vector<float>& detune_q, SchedOut* out) {
