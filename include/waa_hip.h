@@ -319,7 +319,10 @@ waa_status waa_oscillator_set_periodic_wave(waa_batch* batch, uint32_t node, con
 waa_status waa_oscillator_set_wavetable(waa_batch* batch, uint32_t node, const float* table, uint32_t n);
 /* IIRFilterOptions{feedforward, feedback} (src/node/iir_filter.rs:63-72), shared by all instances; required
  * before waa_render.  1..20 coefficients each (NotSupportedError otherwise), feedforward not all zero and
- * feedback[0] != 0 (InvalidStateError), iir_filter.rs:17-46. */
+ * feedback[0] != 0 (InvalidStateError), iir_filter.rs:17-46.
+ * One set per instance — what in the reference is every context constructing its own IIRFilterNode — is set with
+ * waa_iir_set_coefficients_instance of include/waa_hip_device.h (the device library only: this header is the boundary
+ * the oracle exports too); the set given here then serves the instances without one of their own. */
 #define WAA_MAX_IIR_COEFFS 20
 waa_status waa_iir_set_coefficients(waa_batch* batch, uint32_t node, const double* feedforward, uint32_t n_feedforward,
                                     const double* feedback, uint32_t n_feedback);
@@ -464,7 +467,8 @@ typedef struct waa_sharded_job {
                                   * sub-batch is created anew) when the graph has an edge into an AudioParam: its plan may hold
                                   * values rendered from the sub-batch's own audio (waa_batch_rearm).  A `setup` that hands
                                   * every sub-batch its own slice [first, first + count) of per-instance impulse responses
-                                  * (CONVOLVER i[1] = 1) depends on `first`: leave this 0 there */
+                                  * (CONVOLVER i[1] = 1) or of per-instance IIR coefficient sets
+                                  * (waa_iir_set_coefficients_instance, waa_hip_device.h) depends on `first`: leave this 0 there */
 } waa_sharded_job;
 /* Blocks until every context is rendered and downloaded; *seconds (may be NULL) = wall time.  Pinned host buffers let
  * the transfers run at link speed, and a device arena (waa_device_arena_reserve, once per process) keeps hipMalloc / hipFree —

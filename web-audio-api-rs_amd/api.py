@@ -200,6 +200,12 @@ ABI = {
 }
 
 
+# what include/waa_hip_device.h declares: entry points of the device library alone (the oracle keeps one context's worth of state)
+ABI_DEVICE = {
+    "iir_set_coefficients_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _DP, C.c_uint32, _DP, C.c_uint32]),
+}
+
+
 class Binding:
     """ctypes view of one C-ABI library (prefix ``waa_`` for the product)."""
 
@@ -211,6 +217,19 @@ class Binding:
             fn.restype = restype
             fn.argtypes = argtypes
             setattr(self, name, fn)
+        # the device library's own entry points: bound where the library exports them (another binding, or a build of the device
+        # library from before an entry point existed, does not), an AttributeError on first use otherwise
+        for name, (restype, argtypes) in ABI_DEVICE.items():
+            fn = getattr(lib, prefix + name, None) if prefix == "waa_" else None
+            if fn is not None:
+                fn.restype = restype
+                fn.argtypes = argtypes
+                setattr(self, name, fn)
+
+    def __getattr__(self, name):
+        if name in ABI_DEVICE:
+            raise AttributeError(f"{self.prefix}{name} is an entry point of the device library that this binding's library does not export")
+        raise AttributeError(name)
 
     def check(self, status: int):
         if status != 0:
@@ -1110,38 +1129,92 @@ def _dp(a: np.ndarray):
     return a.ctypes.data_as(_DP)
 
 
+def _iir_coefficients(feedforward, feedback):
+    """IIRFilterOptions validated like the reference's constructor (iir_filter.rs:17-46)"""
+    ff = np.ascontiguousarray(feedforward, dtype=np.float64).reshape(-1)
+    fb = np.ascontiguousarray(feedback, dtype=np.float64).reshape(-1)
+    if not 1 <= ff.size <= MAX_IIR_COEFFS:
+        raise WaaError(2, "NotSupportedError - IIR Filter feedforward coefficients should have length >= 0 and <= 20")
+    if not np.any(ff != 0.0):
+        raise WaaError(3, "InvalidStateError - IIR Filter feedforward coefficients cannot be all zeros")
+    if not 1 <= fb.size <= MAX_IIR_COEFFS:
+        raise WaaError(2, "NotSupportedError - IIR Filter feedback coefficients should have length >= 0 and <= 20")
+    if fb[0] == 0.0:
+        raise WaaError(3, "InvalidStateError - IIR Filter feedback first coefficient cannot be zero")
+    return ff, fb
+
+
 class IIRFilterNode(AudioNode):
-    """src/node/iir_filter.rs:140-263.  Coefficients are fixed at construction (IIRFilterOptions)."""
+    """src/node/iir_filter.rs:140-263.  Coefficients are fixed at construction (IIRFilterOptions); a context of the batch may be
+    given its own set before the render (every context of the reference constructs its own node)."""
 
     kind = NODE_IIR_FILTER
 
     def __init__(self, ctx, feedforward, feedback, **kw):
-        ff = np.ascontiguousarray(feedforward, dtype=np.float64).reshape(-1)
-        fb = np.ascontiguousarray(feedback, dtype=np.float64).reshape(-1)
-        # iir_filter.rs:17-46
-        if not 1 <= ff.size <= MAX_IIR_COEFFS:
-            raise WaaError(2, "NotSupportedError - IIR Filter feedforward coefficients should have length >= 0 and <= 20")
-        if not np.any(ff != 0.0):
-            raise WaaError(3, "InvalidStateError - IIR Filter feedforward coefficients cannot be all zeros")
-        if not 1 <= fb.size <= MAX_IIR_COEFFS:
-            raise WaaError(2, "NotSupportedError - IIR Filter feedback coefficients should have length >= 0 and <= 20")
-        if fb[0] == 0.0:
-            raise WaaError(3, "InvalidStateError - IIR Filter feedback first coefficient cannot be zero")
+        ff, fb = _iir_coefficients(feedforward, feedback)
         super().__init__(ctx, **kw)
         self.feedforward, self.feedback = ff, fb
+        self._inst_coefs = {}  # instance -> (feedforward, feedback): one set per context (waa_iir_set_coefficients_instance)
+
+    def set_coefficients(self, feedforward, feedback, instance: int = ALL):
+        """instance = ALL: the set of every context without one of its own.  instance = i: context i's own IIRFilterOptions;
+        the node then works in per-instance mode.  Lengths may differ between contexts."""
+        ff, fb = _iir_coefficients(feedforward, feedback)
+        if self.context._handle is not None:
+            raise WaaError(3, "InvalidStateError - the batch is frozen once rendering has started")
+        if instance == ALL:
+            self.feedforward, self.feedback = ff, fb
+        else:
+            if not 0 <= int(instance) < self.context.n_instances:
+                raise WaaError(1, f"instance {instance} out of range")
+            self._inst_coefs[int(instance)] = (ff, fb)
+        return self
+
+    def set_coefficients_batch(self, feedforward, feedback):
+        """feedforward [n_instances, nff], feedback [n_instances, nfb]: one set per context."""
+        ff = np.asarray(feedforward, dtype=np.float64)
+        fb = np.asarray(feedback, dtype=np.float64)
+        n = self.context.n_instances
+        if ff.ndim != 2 or fb.ndim != 2 or ff.shape[0] != n or fb.shape[0] != n:
+            raise WaaError(1, f"set_coefficients_batch takes [n_instances = {n}, nff] and [n_instances = {n}, nfb], got {ff.shape} and {fb.shape}")
+        for i in range(n):
+            self.set_coefficients(ff[i], fb[i], instance=i)
+        return self
+
+    @property
+    def per_instance(self) -> bool:
+        return bool(self._inst_coefs)
+
+    def _check_per_instance(self):
+        if self.context._b.prefix != "waa_":
+            raise WaaError(4, "one coefficient set per instance is a feature of the device library; this binding keeps one set "
+                              "per batch (render it one context at a time)")
+
+    def _fill_desc(self, d):
+        if self.per_instance:
+            self._check_per_instance()  # (refusals before the batch exists)
 
     def _apply(self, ctx):
         b, h = ctx._b, ctx._handle
         b.check(b.iir_set_coefficients(h, self.id, _dp(self.feedforward), self.feedforward.size, _dp(self.feedback),
                                        self.feedback.size))
+        if self.per_instance:
+            self._check_per_instance()
+            for i, (ff, fb) in sorted(self._inst_coefs.items()):
+                b.check(b.iir_set_coefficients_instance(h, self.id, i, _dp(ff), ff.size, _dp(fb), fb.size))
 
-    def get_frequency_response(self, frequency_hz) -> tuple:
+    def get_frequency_response(self, frequency_hz, instance: int = ALL) -> tuple:
+        """instance = i: the response of context i's filter (its own set, or the ALL set where it has none)"""
+        ff, fb = self.feedforward, self.feedback
+        if instance != ALL:
+            if not 0 <= int(instance) < self.context.n_instances:
+                raise WaaError(1, f"instance {instance} out of range")
+            ff, fb = self._inst_coefs.get(int(instance), (ff, fb))
         hz = _f32(frequency_hz)
         mag = np.empty_like(hz)
         phase = np.empty_like(hz)
         b = self.context._b
-        b.check(b.iir_frequency_response(_dp(self.feedforward), self.feedforward.size, _dp(self.feedback),
-                                         self.feedback.size, self.context.sample_rate, _fp(hz), _fp(mag), _fp(phase),
+        b.check(b.iir_frequency_response(_dp(ff), ff.size, _dp(fb), fb.size, self.context.sample_rate, _fp(hz), _fp(mag), _fp(phase),
                                          hz.size))
         return mag, phase
 

@@ -6,6 +6,7 @@
 #include <mutex>
 #include <set>
 
+#include "../../include/waa_hip_device.h"
 #include "waa_host.hpp"
 
 namespace waa {
@@ -877,20 +878,43 @@ static int check_iir_coefs(const double* ff, uint32_t nff, const double* fb, uin
   return 0;
 }
 
+// iir_filter.rs:282-309: pad to equal length, divide by a0
+static void normalise_iir_coefs(const double* ff, uint32_t nff, const double* fb, uint32_t nfb, std::vector<double>& nb,
+                                std::vector<double>& na) {
+  const uint32_t len = std::max(nff, nfb);
+  const double a0 = fb[0];
+  nb.assign(len, 0.);
+  na.assign(len, 0.);
+  for (uint32_t i = 0; i < len; i++) {
+    nb[i] = (i < nff ? ff[i] : 0.) / a0;
+    na[i] = (i < nfb ? fb[i] : 0.) / a0;
+  }
+}
+
 waa_status waa_iir_set_coefficients(waa_batch* b, uint32_t node, const double* ff, uint32_t nff, const double* fb,
                                     uint32_t nfb) {
   int e;
   if ((e = check_node(b, node, WAA_NODE_IIR_FILTER)) || (e = check_unplanned(b))) return e;
   if ((e = check_iir_coefs(ff, nff, fb, nfb))) return e;
   Node& n = b->nodes[node];
-  const uint32_t len = std::max(nff, nfb);
-  const double a0 = fb[0];
-  n.iir_b.assign(len, 0.);
-  n.iir_a.assign(len, 0.);
-  for (uint32_t i = 0; i < len; i++) {
-    n.iir_b[i] = (i < nff ? ff[i] : 0.) / a0;
-    n.iir_a[i] = (i < nfb ? fb[i] : 0.) / a0;
+  normalise_iir_coefs(ff, nff, fb, nfb, n.iir_b, n.iir_a);
+  return WAA_OK;
+}
+
+// every context of the reference constructs its own IIRFilterNode (iir_filter.rs:163-189): one set for one instance
+waa_status waa_iir_set_coefficients_instance(waa_batch* b, uint32_t node, uint32_t inst, const double* ff, uint32_t nff,
+                                             const double* fb, uint32_t nfb) {
+  int e;
+  if ((e = check_node(b, node, WAA_NODE_IIR_FILTER)) || (e = check_unplanned(b))) return e;
+  if (inst == WAA_ALL_INSTANCES) return waa_iir_set_coefficients(b, node, ff, nff, fb, nfb);
+  if (inst >= b->n_inst) return fail(WAA_ERR_INVALID_ARGUMENT, "instance %u out of range (IIRFilterNode %u, %u instances)", inst, node, b->n_inst);
+  if ((e = check_iir_coefs(ff, nff, fb, nfb))) return e;
+  Node& n = b->nodes[node];
+  if (!n.per_inst_iir()) {
+    n.iir_inst_b.resize(b->n_inst);
+    n.iir_inst_a.resize(b->n_inst);
   }
+  normalise_iir_coefs(ff, nff, fb, nfb, n.iir_inst_b[inst], n.iir_inst_a[inst]);
   return WAA_OK;
 }
 

@@ -441,8 +441,8 @@ __device__ __forceinline__ void dyn_body(const DynDesc& d) {
               scratch[c * RQ + 64 + lane] = ss ? 0.f : v[c][1];
             }
             lds_sync();
-            if (iir) {  // the coefficient block (shared by all instances) once per quantum into LDS: b then a, zero padded
-              const double* cb = reinterpret_cast<const double*>(op.ptr0);
+            if (iir) {  // the coefficient block (shared by all instances: u0 = 0, or this instance's) once per quantum into LDS: b then a, zero padded
+              const double* cb = reinterpret_cast<const double*>(op.ptr0) + (uint64_t)inst * op.u0;
               for (int j = lane; j < 2 * (ns + 1); j += 64) coef_s[j] = load_global(cb + j);
               lds_sync();
             }

@@ -173,6 +173,12 @@ struct Node {
   std::vector<float> osc_wave;
   // iir filter: normalised coefficient pairs (iir_filter.rs:273-311)
   std::vector<double> iir_b, iir_a;
+  // one set per instance (waa_iir_set_coefficients_instance): [n_inst] once the first instance has its own set, normalised like
+  // the shared pair; an empty entry = that instance uses iir_b / iir_a
+  std::vector<std::vector<double>> iir_inst_b, iir_inst_a;
+  bool per_inst_iir() const { return !iir_inst_b.empty(); }
+  const std::vector<double>& iir_b_of(uint32_t inst) const { return per_inst_iir() && !iir_inst_b[inst].empty() ? iir_inst_b[inst] : iir_b; }
+  const std::vector<double>& iir_a_of(uint32_t inst) const { return per_inst_iir() && !iir_inst_b[inst].empty() ? iir_inst_a[inst] : iir_a; }
   // analyser (control side state): the pulls of ALL instances are computed by one launch and cached until the next render
   // (current_time after an offline render never changes: repeated pulls return the same data, analysis.rs:354-357)
   struct AnBatch {

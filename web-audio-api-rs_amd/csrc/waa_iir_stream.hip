@@ -1,5 +1,7 @@
 // waa_iir_stream.hip — IIRFilterNode (src/node/iir_filter.rs:323-405): f64 transposed direct form II with up
-// to 19 state variables, constant coefficients shared by all instances.
+// to 19 state variables, constant coefficients: one set shared by all instances, or (waa_iir_set_coefficients_instance) one set per
+// instance, zero padded to the node's state count — the PER_INST forms below read the instance's block at d.coef_stride /
+// d.pow_stride doubles per instance.
 //
 // Same streaming shape as the biquad kernel: one 64-lane wavefront per (instance, channel), 2048-frame tiles,
 // LDS transpose so every lane owns 32 consecutive frames.  The recurrence
@@ -33,7 +35,7 @@ __device__ __forceinline__ double shfl_up_zero(double v, int delta, int lane) {
 }
 }  // namespace
 
-template <int NS>
+template <int NS, bool PER_INST>
 __global__ __launch_bounds__(64, 2) void iir_stream_kernel(const IirStreamDesc d) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const uint32_t wid = blockIdx.x;
@@ -48,8 +50,10 @@ __global__ __launch_bounds__(64, 2) void iir_stream_kernel(const IirStreamDesc d
   // normalised coefficients, uniform: cb[0..NS], ca[0..NS] (ca[0] unused)
   // (re-derived from an opaque pointer inside every pass so the scalar loads are not hoisted out of the tile
   // loop: 2 (NS + 1) + 6 NS^2 loop-invariant doubles would not fit the SGPR file and spill)
-  const cdouble_ptr coef_c = (cdouble_ptr)(d.coef);
-  const cdouble_ptr pw_c = (cdouble_ptr)(d.pow);
+  // (per instance: the instance's blocks — `inst` comes from the block index, so the offsets are wave-uniform and the loads
+  // stay scalar loads)
+  const cdouble_ptr coef_c = (cdouble_ptr)(d.coef) + (PER_INST ? (uint64_t)inst * d.coef_stride : 0);
+  const cdouble_ptr pw_c = (cdouble_ptr)(d.pow) + (PER_INST ? (uint64_t)inst * d.pow_stride : 0);
   auto opaque_zero = []() __attribute__((always_inline)) {
     int z;
     asm volatile("s_mov_b32 %0, 0" : "=s"(z));
@@ -289,7 +293,9 @@ __global__ __launch_bounds__(64, 2) void iir_stream_kernel(const IirStreamDesc d
 // would amplify rounding differences beyond the parity tolerance) or overflows: one LANE per (instance, channel)
 // stream, frames strictly in order, the reference's arithmetic including the explicit flush.  No cross-lane
 // traffic at all; 64-byte runs per lane keep whole sectors in use.  Latency-bound (n_inst * nch / 64 waves).
-template <int NS>
+// PER_INST: every lane keeps its own instance's 2 NS + 1 coefficients in registers (loaded once) instead of reading the shared
+// set through scalar loads.
+template <int NS, bool PER_INST>
 __global__ __launch_bounds__(64) void iir_lane_kernel(const IirStreamDesc d) {
   const uint32_t sid = blockIdx.x * 64 + threadIdx.x;
   if (sid >= d.n_inst * (uint32_t)d.nch) return;
@@ -297,6 +303,17 @@ __global__ __launch_bounds__(64) void iir_lane_kernel(const IirStreamDesc d) {
   const int ch = (int)(sid % (uint32_t)d.nch);
   __builtin_amdgcn_s_setreg(1 | (6 << 6) | (1 << 11), 0);
   const cdouble_ptr cb = (cdouble_ptr)(d.coef), ca = cb + (NS + 1);
+  double vb[PER_INST ? NS + 1 : 1], va[PER_INST ? NS + 1 : 1];  // va[0] unused
+  if constexpr (PER_INST) {
+    const double* cf = d.coef + (uint64_t)inst * d.coef_stride;
+#pragma unroll
+    for (int k = 0; k <= NS; k++) {
+      vb[k] = cf[k];
+      va[k] = cf[NS + 1 + k];
+    }
+  }
+  auto B = [&](int k) __attribute__((always_inline)) { if constexpr (PER_INST) return vb[k]; else return cb[k]; };
+  auto A = [&](int k) __attribute__((always_inline)) { if constexpr (PER_INST) return va[k]; else return ca[k]; };
   const float* ip = d.in.sig.base + (uint64_t)inst * d.in.sig.inst_stride + (uint64_t)ch * d.in.sig.ch_stride;
   float* op = d.out.base + (uint64_t)inst * d.out.inst_stride + (uint64_t)ch * d.out.ch_stride;
   double* st = d.state + ((uint64_t)inst * d.nch + ch) * NS;
@@ -329,13 +346,13 @@ __global__ __launch_bounds__(64) void iir_lane_kernel(const IirStreamDesc d) {
     for (int i = 0; i < BLK; i++) {
       double xd = (double)x[i];
       if (i >= AHEAD) asm volatile("" : "+v"(xd) : "v"(yh[i - AHEAD]));
-      double y = __builtin_fma(cb[0], xd, s[0]);
+      double y = __builtin_fma(B(0), xd, s[0]);
       if (!__builtin_isnormal(y)) y = 0.;
       yh[i] = y;
 #pragma unroll
       for (int k = 0; k < NS; k++) {
         const double next = k + 1 < NS ? s[k + 1] : 0.;
-        s[k] = (cb[k + 1] * xd - ca[k + 1] * y) + next;
+        s[k] = (B(k + 1) * xd - A(k + 1) * y) + next;
       }
       y4[i] = (float)y;
     }
@@ -352,7 +369,10 @@ __global__ __launch_bounds__(64) void iir_lane_kernel(const IirStreamDesc d) {
 // state from its right neighbour (row shift) and updates its own states: the dependent chain per frame is the
 // same handful of operations as in the scalar loop, but the NS-wide part runs across lanes instead of in time,
 // and 16x more wavefronts are in flight than with one lane per stream.  Arithmetic identical to the reference.
-template <int M>
+// The coefficients live in registers per lane.  PER_INST: every row loads them from its own stream's instance (d.coef_stride doubles
+// per instance), so the four rows of a wave may hold four different filters; the row of a partial last wave that is kept busy on
+// the last valid stream reads that stream's instance: an address inside the block.
+template <int M, bool PER_INST>
 __global__ __launch_bounds__(64) void iir_row_kernel(const IirStreamDesc d) {
   const int lane = threadIdx.x, j = lane & 15;
   const uint32_t n_streams = d.n_inst * (uint32_t)d.nch;
@@ -363,15 +383,16 @@ __global__ __launch_bounds__(64) void iir_row_kernel(const IirStreamDesc d) {
   const int ch = (int)(sid % (uint32_t)d.nch);
   __builtin_amdgcn_s_setreg(1 | (6 << 6) | (1 << 11), 0);
   const int ns = d.ns;
-  const double b0 = d.coef[0];
+  const double* cf = PER_INST ? d.coef + (uint64_t)inst * d.coef_stride : d.coef;
+  const double b0 = cf[0];
   double bk[M], ak[M], s[M];
   double* st = d.state + ((uint64_t)inst * d.nch + ch) * ns;
   bool last = false;  // this lane owns s_{ns-1}: its successor is the constant 0 (iir_filter.rs:389-392)
 #pragma unroll
   for (int t = 0; t < M; t++) {
     const int k = j * M + t;
-    bk[t] = k < ns ? d.coef[k + 1] : 0.;
-    ak[t] = k < ns ? d.coef[ns + 1 + k + 1] : 0.;
+    bk[t] = k < ns ? cf[k + 1] : 0.;
+    ak[t] = k < ns ? cf[ns + 1 + k + 1] : 0.;
     s[t] = k < ns ? st[k] : 0.;
     if (t == M - 1) last = k >= ns - 1;
   }
@@ -424,21 +445,38 @@ __global__ __launch_bounds__(64) void iir_row_kernel(const IirStreamDesc d) {
   }
 }
 
+#ifndef WAA_IIR_PER_INST_TU
 int iir_padded_states(int n_states) {  // every order has its own instantiation: no zero-padded states
   if (n_states < 1) return 1;  // a pure gain b0 still runs as a one-state filter with zero coefficients
   return n_states <= 19 ? n_states : -1;
 }
+#endif
 
+// This file is compiled twice: as itself with the shared forms, and through waa_iir_inst.hip (WAA_IIR_PER_INST_TU) with the
+// per-instance forms of the three kernels.  Two code objects, each loaded when its first kernel is launched: with all 80
+// instantiations in one, a process that only ever renders shared coefficients paid 2 ms more for its first render ("Two code objects").
 namespace {
+#ifdef WAA_IIR_PER_INST_TU
+constexpr bool PER_INST_TU = true;
+#else
+constexpr bool PER_INST_TU = false;
+#endif
+void launch_row(const IirStreamDesc& d, hipStream_t s) {
+  const dim3 grid((d.n_inst * (uint32_t)d.nch + 3) / 4), block(64);
+  if (d.ns <= 16)
+    hipLaunchKernelGGL((iir_row_kernel<1, PER_INST_TU>), grid, block, 0, s, d);
+  else
+    hipLaunchKernelGGL((iir_row_kernel<2, PER_INST_TU>), grid, block, 0, s, d);
+}
 template <int NS>
 void launch_ns(const IirStreamDesc& d, hipStream_t s) {
   if (d.exact == 1) {
     const dim3 grid((d.n_inst * (uint32_t)d.nch + 63) / 64), block(64);
-    hipLaunchKernelGGL((iir_lane_kernel<NS>), grid, block, 0, s, d);
+    hipLaunchKernelGGL((iir_lane_kernel<NS, PER_INST_TU>), grid, block, 0, s, d);
   } else {
     const dim3 grid(d.n_inst * (uint32_t)d.nch), block(64);
     const size_t lds = 2 * 64 * LDS_ROW * sizeof(float);
-    hipLaunchKernelGGL((iir_stream_kernel<NS>), grid, block, lds, s, d);
+    hipLaunchKernelGGL((iir_stream_kernel<NS, PER_INST_TU>), grid, block, lds, s, d);
   }
 }
 template <int NS>
@@ -452,17 +490,20 @@ void dispatch_ns(const IirStreamDesc& d, hipStream_t s) {
 }
 }  // namespace
 
+#ifdef WAA_IIR_PER_INST_TU
+void launch_iir_stream_inst(const IirStreamDesc& d, void* stream) {
+  if (d.exact == 2) return launch_row(d, (hipStream_t)stream);
+  dispatch_ns<19>(d, (hipStream_t)stream);
+}
+#else
+void launch_iir_stream_inst(const IirStreamDesc& d, void* stream);  // waa_iir_inst.hip
+
 void launch_iir_stream(const IirStreamDesc& d, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (d.exact == 2) {
-    const dim3 grid((d.n_inst * (uint32_t)d.nch + 3) / 4), block(64);
-    if (d.ns <= 16)
-      hipLaunchKernelGGL((iir_row_kernel<1>), grid, block, 0, s, d);
-    else
-      hipLaunchKernelGGL((iir_row_kernel<2>), grid, block, 0, s, d);
-    return;
-  }
+  if (d.coef_stride != 0) return launch_iir_stream_inst(d, stream);  // one set per instance
+  if (d.exact == 2) return launch_row(d, s);
   dispatch_ns<19>(d, s);
 }
+#endif
 
 }  // namespace waa

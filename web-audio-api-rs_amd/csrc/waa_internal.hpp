@@ -130,7 +130,7 @@ struct OpDesc {
   int32_t kind;
   int32_t nch_in;
   int32_t nch_out;
-  int32_t i1;        // PARAM_ADD: max value (float bits)
+  int32_t i1;        // PARAM_ADD: max value (float bits); IIR: distinct coefficient sets of a per-instance node (0: shared)
   int32_t i2;        // PARAM_ADD: default value (float bits)
   int32_t i0;        // MIX: interpretation; WAVESHAPER: curve length; BIQUAD: coef mode (0 per inst, 1 per quantum, 2 per frame); IIR: padded state count, negative = exact lane kernel; PARAM_ADD: min value (float bits)
   ParamRef p0;       // GAIN: gain; STEREO_PAN: pan; PANNER: azimuth (wrapped)
@@ -138,10 +138,10 @@ struct OpDesc {
   ParamRef p2;       // STEREO_PAN / PANNER: gain_r
   ParamRef p3;       // PANNER: dist_gain*cone_gain factors (dist), p4 (cone)
   ParamRef p4;
-  const void* ptr0;  // WAVESHAPER: curve; BIQUAD: coefficients (double[5] per inst or per inst*quantum); IIR: coef block
+  const void* ptr0;  // WAVESHAPER: curve; BIQUAD: coefficients (double[5] per inst or per inst*quantum); IIR: coef block ([2][ns+1], per instance at stride u0)
   void* ptr1;        // BIQUAD: state double[nch][4] per instance; IIR: state double[nch][ns] per instance
   const void* ptr2;  // IIR: matrix powers
-  uint64_t u0;       // BIQUAD: coefficient stride per instance (in doubles)
+  uint64_t u0;       // BIQUAD: coefficient stride per instance (in doubles); IIR: the same, 0 = one block shared by all instances
 };
 
 struct ChainDesc {
@@ -224,12 +224,13 @@ void launch_biquad_tile_digest(const BiquadLanesDesc& d, void* stream);
 void launch_biquad_lanes(const BiquadLanesDesc& d, void* stream);
 
 // ---- streaming IIR kernel (IIRFilterNode, iir_filter.rs:323-405) -----------------------------
-// input (source or signal) -> transposed direct form II with ns state variables -> output; coefficients are
-// shared by all instances (they are constructor arguments of the node).
+// input (source or signal) -> transposed direct form II with ns state variables -> output; coefficients are constructor
+// arguments of the node: one set shared by all instances (coef_stride = 0), or one set per instance
+// (waa_iir_set_coefficients_instance), every instance zero padded to the node's ns.
 struct IirStreamDesc {
   InputRef in;
-  const double* coef;  // [2][ns+1]: normalised feedforward b[0..ns], then feedback a[0..ns], zero padded
-  const double* pow;   // [6][ns][ns]: M^(32 * 2^k), M = zero-input state transition
+  const double* coef;  // [2][ns+1]: normalised feedforward b[0..ns], then feedback a[0..ns], zero padded; per instance: [n_inst][2][ns+1]
+  const double* pow;   // [6][ns][ns]: M^(32 * 2^k), M = zero-input state transition; per instance: [n_inst][6][ns][ns] (scan kernel only)
   double* state;       // [n_inst][nch][ns]
   int32_t ns;          // state count (1..19)
   int32_t nch;
@@ -239,6 +240,7 @@ struct IirStreamDesc {
   uint32_t n_quanta;
   uint32_t exact;      // 0: scan kernel; exact kernels (input must be IN_SIGNAL): 1 lane per stream, 2 DPP row per stream
   uint32_t tile0, tile1;
+  uint32_t coef_stride, pow_stride;  // doubles from one instance's block to the next; 0: one block for all instances
 };
 int iir_padded_states(int n_states);  // kernel state count for a filter with n_states state variables
 void launch_iir_stream(const IirStreamDesc& d, void* stream);

@@ -746,6 +746,8 @@ int emit_segments(waa_batch* b, std::vector<InputRef> inputs, int in_nch, int in
       q.pow = reinterpret_cast<const double*>(o.ptr2);
       q.state = reinterpret_cast<double*>(o.ptr1);
       q.ns = std::abs(o.i0);
+      q.coef_stride = (uint32_t)o.u0;  // one set per instance: every kernel below reads its instance's block
+      q.pow_stride = o.u0 && !iir_exact ? 6u * (uint32_t)(q.ns * q.ns) : 0u;
       // exact kernels: one lane per stream pays off for low orders or very many streams, one DPP row per
       // stream otherwise (issue cycles per frame: ~12 ns + 32 per 64 streams vs ~64 per 4 streams, on 1024 SIMDs)
       q.exact = 0u;
@@ -762,12 +764,14 @@ int emit_segments(waa_batch* b, std::vector<InputRef> inputs, int in_nch, int in
       q.tile0 = 0;
       q.tile1 = b->n_tiles;
       q.n_quanta = b->n_quanta;
-      char name[32];
-      snprintf(name, sizeof name, "%s<%d>", q.exact == 2 ? "iir_row_kernel" : q.exact == 1 ? "iir_lane_kernel" : "iir_stream_kernel", q.ns);
+      char name[40], per[40] = "";
+      snprintf(name, sizeof name, "%s<%d%s>", q.exact == 2 ? "iir_row_kernel" : q.exact == 1 ? "iir_lane_kernel" : "iir_stream_kernel", q.ns,
+               q.coef_stride ? ",inst" : "");
       st.profile_slot = slot_for(b, name);
       b->steps.push_back(st);
-      plan_note(b, "%s states=%d in=%s:%dch out=%s", q.exact == 2 ? "iir_exact(row)" : q.exact == 1 ? "iir_exact(lane)" : "iir_stream", q.ns,
-                input_kind_name(inputs[0].kind), cur_nch, seg_out.base == out.base ? "final" : "temp");
+      if (q.coef_stride) snprintf(per, sizeof per, " coef=per-instance(%d)", o.i1);
+      plan_note(b, "%s states=%d in=%s:%dch out=%s%s", q.exact == 2 ? "iir_exact(row)" : q.exact == 1 ? "iir_exact(lane)" : "iir_stream", q.ns,
+                input_kind_name(inputs[0].kind), cur_nch, seg_out.base == out.base ? "final" : "temp", per);
       InputRef in{};
       in.kind = IN_SIGNAL;
       in.nch = cur_nch;
@@ -1066,8 +1070,13 @@ static int build_plan_impl(waa_batch* b) {
   std::unique_ptr<PlanTrace> ph(new PlanTrace("phase: automation + order + loops + counts"));
   if (int e = materialise_automation(b)) return e;
   for (uint32_t i = 0; i < N; i++)  // the reference takes the coefficients in the constructor
-    if (b->nodes[i].desc.kind == WAA_NODE_IIR_FILTER && b->nodes[i].iir_b.empty())
-      return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - IIRFilterNode %u has no coefficients", i);
+    if (b->nodes[i].desc.kind == WAA_NODE_IIR_FILTER && b->nodes[i].iir_b.empty()) {
+      const Node& n = b->nodes[i];
+      if (!n.per_inst_iir()) return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - IIRFilterNode %u has no coefficients", i);
+      for (uint32_t inst = 0; inst < b->n_inst; inst++)  // (no set for ALL: every instance needs its own)
+        if (n.iir_inst_b[inst].empty())
+          return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - IIRFilterNode %u has no coefficients for instance %u", i, inst);
+    }
   // processing order = reversed DFS post-order over outgoing edges in insertion order, cycle breakers applied
   // (graph.rs:323-487); `items` has two entries per DelayNode (writer, reader), none for muted nodes
   std::vector<uint32_t> items;

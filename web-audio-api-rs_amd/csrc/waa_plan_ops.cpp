@@ -1,7 +1,9 @@
 // waa_plan_ops.cpp — a node as chain ops (emit_node_ops) and the per-kind channel configuration defaults (split out of
 // waa_plan.cpp in round 4).
 #include <array>
+#include <map>
 #include <set>
+#include <string>
 
 #include "waa_host.hpp"
 #include "waa_plan_parts.hpp"
@@ -144,17 +146,29 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
     }
     case WAA_NODE_IIR_FILTER: {
       // iir_filter.rs:323-405.  N = len - 1 state variables, padded with zero coefficients to a kernel size.
+      // One set per instance (waa_iir_set_coefficients_instance): the node's state count is the longest instance's, every
+      // instance is padded with zero coefficients to it (exact for finite input), the coefficient block is
+      // [n_inst][2][ns + 1] and the block of matrix powers [n_inst][6][ns][ns].
       OpDesc o{};
       o.kind = OP_IIR;
       o.nch_in = o.nch_out = nch;
-      const int len = (int)n.iir_b.size();
+      const bool per_inst = n.per_inst_iir();
+      const uint32_t n_sets = per_inst ? b->n_inst : 1u;
+      int len = 0;
+      for (uint32_t i = 0; i < n_sets; i++) len = std::max(len, (int)n.iir_b_of(i).size());
       const int ns = iir_padded_states(len - 1);
       if (ns < 0) return fail(WAA_ERR_DEVICE, "internal: IIR order");
-      std::vector<double> co(2 * (size_t)(ns + 1), 0.);
-      for (int k = 0; k < len; k++) {
-        co[k] = n.iir_b[k];
-        co[ns + 1 + k] = n.iir_a[k];
+      const size_t cstride = 2 * (size_t)(ns + 1), pstride = 6 * (size_t)ns * ns;
+      std::vector<double> co(n_sets * cstride, 0.);
+      for (uint32_t i = 0; i < n_sets; i++) {
+        const std::vector<double>&ib = n.iir_b_of(i), &ia = n.iir_a_of(i);
+        for (size_t k = 0; k < ib.size(); k++) {
+          co[i * cstride + k] = ib[k];
+          co[i * cstride + ns + 1 + k] = ia[k];
+        }
       }
+      const char* genv = measure_switch("WAA_IIR_GROWTH");  // experiments only
+      const double growth_limit = genv ? atof(genv) : 1e4;
       // zero-input state transition M: s_i' = -a_{i+1} s_0 + s_{i+1}; powers M^(32 * 2^k), k = 0..5, for the
       // lane scan of the kernel (double-double on the host, rounded once).  `growth` = largest entry of any power
       // the scan can form (intermediate squarings and all A^j, j <= 64): the scan's rounding error relative to
@@ -162,47 +176,60 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
       // and unstable filters go to the exact lane-per-stream kernel instead.
       // (double-double arithmetic, ~106 bits: repeated squaring of a matrix with large transient entries loses
       // growth^2 * eps per step, which long double cannot absorb for the filters that are still worth scanning)
-      std::vector<DD> m((size_t)ns * ns), t((size_t)ns * ns);
-      for (int i = 0; i < ns; i++) {
-        m[(size_t)i * ns] = DD{-co[ns + 1 + i + 1], 0.};
-        if (i + 1 < ns) m[(size_t)i * ns + i + 1] = dd_add(m[(size_t)i * ns + i + 1], DD{1., 0.});
-      }
-      double growth = 0.;
-      auto note = [&](const std::vector<DD>& a) {
-        for (const DD& v : a) growth = std::isfinite(v.hi) ? std::max(growth, std::fabs(v.hi)) : INFINITY;
+      // Returns false as soon as the growth passes the limit (the powers are not used then).
+      auto powers = [&](const double* cf, double* pw) -> bool {
+        std::vector<DD> m((size_t)ns * ns), t((size_t)ns * ns);
+        for (int i = 0; i < ns; i++) {
+          m[(size_t)i * ns] = DD{-cf[ns + 1 + i + 1], 0.};
+          if (i + 1 < ns) m[(size_t)i * ns + i + 1] = dd_add(m[(size_t)i * ns + i + 1], DD{1., 0.});
+        }
+        double growth = 0.;
+        auto note = [&](const std::vector<DD>& a) {
+          for (const DD& v : a) growth = std::isfinite(v.hi) ? std::max(growth, std::fabs(v.hi)) : INFINITY;
+          return growth <= growth_limit;
+        };
+        auto mul = [&](const std::vector<DD>& x, const std::vector<DD>& y, std::vector<DD>& out) {
+          for (int r = 0; r < ns; r++)
+            for (int c = 0; c < ns; c++) {
+              DD acc{0., 0.};
+              for (int k = 0; k < ns; k++) acc = dd_add(acc, dd_mul(x[(size_t)r * ns + k], y[(size_t)k * ns + c]));
+              out[(size_t)r * ns + c] = acc;
+            }
+        };
+        for (int k = 0; k < 5; k++) {  // M^32
+          mul(m, m, t);
+          m.swap(t);
+          if (!note(m)) return false;
+        }
+        const std::vector<DD> A = m;
+        for (int lvl = 0; lvl < 6; lvl++) {
+          for (size_t k = 0; k < (size_t)ns * ns; k++) pw[lvl * (size_t)ns * ns + k] = m[k].hi + m[k].lo;
+          mul(m, m, t);
+          m.swap(t);
+          if (!note(m)) return false;
+        }
+        m = A;
+        for (int j = 2; j <= 64; j++) {  // every A^j a lane can see
+          mul(m, A, t);
+          m.swap(t);
+          if (!note(m)) return false;
+        }
+        return true;
       };
-      auto mul = [&](const std::vector<DD>& x, const std::vector<DD>& y, std::vector<DD>& out) {
-        for (int r = 0; r < ns; r++)
-          for (int c = 0; c < ns; c++) {
-            DD acc{0., 0.};
-            for (int k = 0; k < ns; k++) acc = dd_add(acc, dd_mul(x[(size_t)r * ns + k], y[(size_t)k * ns + c]));
-            out[(size_t)r * ns + c] = acc;
-          }
-      };
-      for (int k = 0; k < 5; k++) {  // M^32
-        mul(m, m, t);
-        m.swap(t);
-        note(m);
+      // the powers once per distinct set (by the bytes of the normalised, padded coefficients: a sweep repeats sets, and the
+      // instances without a set of their own all hold the shared one).  One instance over the limit: the whole node is exact.
+      bool exact = getenv("WAA_IIR_EXACT") != nullptr;  // env: debugging aid
+      std::vector<double> pw(n_sets * pstride, 0.);
+      std::map<std::string, uint32_t> seen;
+      for (uint32_t i = 0; i < n_sets; i++) {
+        const auto at = seen.emplace(std::string(reinterpret_cast<const char*>(&co[i * cstride]), cstride * sizeof(double)), i);
+        if (exact) continue;  // (still counting the distinct sets)
+        if (!at.second)
+          std::copy_n(&pw[at.first->second * pstride], pstride, &pw[i * pstride]);
+        else if (!powers(&co[i * cstride], &pw[i * pstride]))
+          exact = true;
       }
-      const std::vector<DD> A = m;
-      std::vector<double> pw(6 * (size_t)ns * ns);
-      for (int lvl = 0; lvl < 6; lvl++) {
-        for (size_t k = 0; k < (size_t)ns * ns; k++) pw[lvl * (size_t)ns * ns + k] = m[k].hi + m[k].lo;
-        mul(m, m, t);
-        m.swap(t);
-        note(m);
-      }
-      m = A;
-      for (int j = 2; j <= 64 && std::isfinite(growth); j++) {  // every A^j a lane can see
-        mul(m, A, t);
-        m.swap(t);
-        note(m);
-      }
-      const char* genv = measure_switch("WAA_IIR_GROWTH");  // experiments only
-      const double growth_limit = genv ? atof(genv) : 1e4;
-      const bool exact = !(growth <= growth_limit) || getenv("WAA_IIR_EXACT") != nullptr;  // env: debugging aid
-      if (exact)
-        for (auto& v : pw) v = 0.;  // unused
+      if (exact) pw.assign(pstride, 0.);  // unused
       double *dco = nullptr, *dpw = nullptr, *dst = nullptr;
       int e;
       if ((e = dev_upload(b, &dco, co)) || (e = dev_upload(b, &dpw, pw))) return e;
@@ -210,9 +237,11 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
       if ((e = dev_alloc(b, &dst, n_state))) return e;
       b->state_bufs.push_back({dst, n_state * sizeof(double)});
       o.i0 = exact ? -ns : ns;
+      o.i1 = per_inst ? (int32_t)seen.size() : 0;  // distinct sets (plan note)
       o.ptr0 = dco;
       o.ptr1 = dst;
       o.ptr2 = dpw;
+      o.u0 = per_inst ? cstride : 0;
       ops.push_back(o);
       break;
     }

@@ -6,8 +6,9 @@ rendered together (include/waa_hip.h) — so a serving host has to sort its cont
 step for the Python mirror (round-5 review, missing 4): contexts built one by one, exactly like reference contexts
 (`OfflineAudioContext(channels, length, rate)` with n_instances = 1), are bucketed by `shape_key` — the graph (node kinds, options,
 channel configuration, connections), the context's format, the SHAPES of per-context payloads (an AudioBufferSource's channel count,
-length and rate) and the identity of payloads a batch shares (a convolver's impulse response, a shaper's curve, IIR coefficients,
-a periodic wave) — every bucket is merged into one batch (per-context AudioBuffers, AudioParam values and automation, start / stop /
+length and rate, and on the device library the padded length of an IIRFilterNode's coefficients, which become per-instance sets of the
+batch) and the identity of payloads a batch shares (a convolver's impulse response, a shaper's curve, a periodic wave, IIR
+coefficients on other bindings) — every bucket is merged into one batch (per-context AudioBuffers, AudioParam values and automation, start / stop /
 loop settings become per-instance settings of the batch), rendered, and the AudioBuffers are handed back in the callers' order.
 Contexts with suspend callbacks render on their own (their callbacks may do anything)."""
 from __future__ import annotations
@@ -26,6 +27,11 @@ def _digest(a) -> str:
     return hashlib.sha1(a.tobytes()).hexdigest()[:16] + str(a.shape) + str(a.dtype)
 
 
+def _iir_set(nd):
+    """the coefficients context 0 of an IIRFilterNode renders with"""
+    return nd._inst_coefs.get(0, (nd.feedforward, nd.feedback))
+
+
 def _node_key(nd) -> tuple:
     d = nd._desc()
     key = [type(nd).__name__, int(d.kind), int(d.channel_count), int(d.channel_count_mode), int(d.channel_interpretation),
@@ -38,7 +44,13 @@ def _node_key(nd) -> tuple:
         curve = getattr(nd, "curve", None)
         key.append(None if curve is None else _digest(curve))
     if isinstance(nd, IIRFilterNode):
-        key.append((_digest(nd.feedforward), _digest(nd.feedback)))
+        ff, fb = _iir_set(nd)  # (a single context's own set: its instance-0 set if it was given one, else the constructor's)
+        if nd.context._b.prefix == "waa_":
+            # the device library takes one set per context: contexts that differ only in their coefficients share a batch; the
+            # padded length (iir_filter.rs:282-309) stays in the key, so a batch never pays for a longer filter than its own
+            key.append(("iir-len", max(ff.size, fb.size)))
+        else:
+            key.append((_digest(ff), _digest(fb)))
     if isinstance(nd, OscillatorNode) and nd.periodic_wave is not None:
         w = nd.periodic_wave
         key.append(_digest(w.table) if w.table is not None else (_digest(w.real), _digest(w.imag), w.disable_normalization))
@@ -105,6 +117,14 @@ def _merge(bucket: Sequence[OfflineAudioContext]) -> OfflineAudioContext:
                         cn._starts[i] = o._starts[ALL]
                     if ALL in o._stops:
                         cn._stops[i] = o._stops[ALL]
+        if isinstance(cn, IIRFilterNode):
+            # every context's effective set (_iir_set) becomes its instance's; equal sets everywhere: the node stays shared
+            sets = [_iir_set(nd) for nd in [cn] + others]
+            cn._inst_coefs = {}
+            cn.feedforward, cn.feedback = sets[0]
+            if not all(np.array_equal(ff, sets[0][0]) and np.array_equal(fb, sets[0][1]) for ff, fb in sets[1:]):
+                for i, (ff, fb) in enumerate(sets[1:], start=1):
+                    cn.set_coefficients(ff, fb, instance=i)
         if isinstance(cn, AudioBufferSourceNode):
             if not all(o._buffers.get(ALL) is cn._buffers.get(ALL) for o in others):
                 if ALL in cn._buffers:

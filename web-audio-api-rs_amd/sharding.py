@@ -99,7 +99,7 @@ def _host_block(a, name, dtype, shape_tail=None):
 
 def render_sharded(build: Callable, host_in, host_out, devices: Sequence[int] = (0,), sub_batches: int = 8,
                    sample_rate: float = 48000.0, pcm16: bool = False, pull: Optional[Callable] = None, out_pcm16: bool = False,
-                   reuse: bool = False):
+                   reuse: bool = False, pass_first: bool = False):
     """Render N contexts whose source AudioBuffers live on the host, on one or several GPUs: a thin caller of the library's
     waa_render_sharded (include/waa_hip.h; csrc/waa_sharded.cpp — contiguous ranges per device, sub-batches pipelined
     upload || render || download, one host thread per sub-batch inside the library).
@@ -107,6 +107,9 @@ def render_sharded(build: Callable, host_in, host_out, devices: Sequence[int] = 
     build(n_instances, device) -> (ctx, src): builds the (identical) graph for a sub-batch of `n_instances` contexts on
         `device`; `src` is the AudioBufferSourceNode that receives the contexts' buffers.  Called once for the graph's shape
         and once per sub-batch (on the library's thread) to configure that sub-batch: node payloads, params, schedules.
+    pass_first: build is called as build(n_instances, device, first=k) with the index of the sub-batch's first context (0 for the
+        shape), for payloads that differ from context to context (per-instance impulse responses, per-instance IIR coefficients):
+        it configures contexts [k, k + n_instances).  Leave `reuse` off then.
     host_in:  [N, channels, frames] float32 — or, with pcm16=True, [N, frames, channels] int16 (decoded WAV data: half
         the upload, converted on the device) — C-contiguous numpy array or pinned torch tensor.
     host_out: [N, n_out, length] float32 (out_pcm16=True: [N, length, n_out] int16), filled with every context's AudioBuffer.
@@ -123,7 +126,7 @@ def render_sharded(build: Callable, host_in, host_out, devices: Sequence[int] = 
     base_in, shape_in = _host_block(host_in, "host_in", np.int16 if pcm16 else np.float32)
     n_total = shape_in[0]
     frames, n_ch = (shape_in[1], shape_in[2]) if pcm16 else (shape_in[2], shape_in[1])
-    tmpl, tsrc = build(1, devices[0])
+    tmpl, tsrc = build(1, devices[0], first=0) if pass_first else build(1, devices[0])
     tail = (tmpl.length, tmpl.number_of_channels) if out_pcm16 else (tmpl.number_of_channels, tmpl.length)
     base_out, shape_out = _host_block(host_out, "host_out", np.int16 if out_pcm16 else np.float32, tail)
     if shape_out[0] != n_total:
@@ -134,7 +137,7 @@ def render_sharded(build: Callable, host_in, host_out, devices: Sequence[int] = 
 
     def setup(handle, first, count, device, _user):
         try:
-            ctx, _ = build(int(count), int(device))
+            ctx, _ = build(int(count), int(device), first=int(first)) if pass_first else build(int(count), int(device))
             if len(ctx._nodes) != graph.n_nodes:
                 raise WaaError(1, "render_sharded: build() must return the same graph for every sub-batch")
             live[int(first)] = ctx  # (before _adopt: whatever happens below, the finally clause forgets the library's handle)
