@@ -2929,6 +2929,10 @@ static double osc_poly_blep(double t, double dt) { /* :630-643 (production: cfg!
   }
   return 0.0;
 }
+/* As in the reference, a phase of exactly 1.0 would index table[len]: osc_unroll_phase returns 1.0 for a phase in
+ * [-2^-54, 0) (phase + 1. rounds up), reachable when |phase + incr| < 2^-54.  The reference panics there; the oracle is
+ * left as the reference is written, and no test steers into it (tests/test_oscillator_kernels.py keeps |incr| >= 1e-9
+ * or exactly 0).  The device's table_sample (waa_osc.hip) wraps that index to 0. */
 static float osc_table_sample(const float* table, int len, double phase) { /* :571-586, :604-619 */
   double position = phase * (double)len;
   double floored = floor(position);

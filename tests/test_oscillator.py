@@ -462,13 +462,21 @@ def _two_operator(binding, n, frames, variant, plan_only=False):
     no-gain      the modulator connected straight to the param
     clamped      an index large enough to drive the sum past the param's range (the clamp of mix_to_output) and below zero
     shared       the modulator ALSO reaches the destination (it has a second reader: not folded)
-    two-mods     two modulators summed on the param (more than one input: not folded)"""
+    two-mods     two modulators summed on the param (more than one input: not folded)
+    saw-mod      a sawtooth modulator (the folded fm_type dispatch), context 1 with a NEGATIVE modulator frequency (hard steps)
+    custom-mod   a finished 8192-point table as the modulator (fm_table / fm_table_len), context 1 negative as well"""
     kw = {"device": waa.PLAN_ONLY} if plan_only else {}
     c = waa.OfflineAudioContext(1, frames, 48000.0, n_instances=n, binding=binding, **kw)
-    mod = c.create_oscillator(type_="square" if variant == "square-mod" else "sine", frequency=110.0)
+    if variant == "custom-mod":
+        i = np.arange(8192, dtype=np.float64) / 8192.0
+        table = np.sin(2 * np.pi * i) + 0.5 * np.sin(6 * np.pi * i + 0.3) + 0.1 * np.random.default_rng(11).uniform(-1.0, 1.0, 8192)
+        mod = c.create_oscillator(frequency=110.0, periodic_wave=waa.PeriodicWave.from_wavetable((table / np.abs(table).max()).astype(np.float32)))
+    else:
+        mod = c.create_oscillator(type_={"square-mod": "square", "saw-mod": "sawtooth"}.get(variant, "sine"), frequency=110.0)
     car = c.create_oscillator(type_="sine", frequency=440.0)
     for i in range(n):
-        mod.frequency.set_value(90.0 + 13.0 * i, instance=i)
+        sign = -1.0 if variant in ("saw-mod", "custom-mod") and i == 1 else 1.0
+        mod.frequency.set_value(sign * (90.0 + 13.0 * i), instance=i)
         car.detune.set_value(30.0 * i, instance=i)
     head = mod
     if variant != "no-gain":
@@ -502,7 +510,7 @@ def _two_operator(binding, n, frames, variant, plan_only=False):
     return out, plan
 
 
-FM_VARIANTS = ["plain", "square-mod", "ramped-index", "no-gain", "clamped", "shared", "two-mods"]
+FM_VARIANTS = ["plain", "square-mod", "ramped-index", "no-gain", "clamped", "shared", "two-mods", "saw-mod", "custom-mod"]
 FM_NOT_FOLDED = ("ramped-index", "shared", "two-mods")
 
 

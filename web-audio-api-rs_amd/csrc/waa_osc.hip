@@ -34,7 +34,10 @@ __device__ __forceinline__ double poly_blep(double t, double dt) {  // :626-643 
 __device__ __forceinline__ float table_sample(const float* table, int len, double phase) {  // :571-586, :604-619
   const double position = phase * (double)len;
   const double floored = floor(position);
-  const int prev_index = (int)floored;
+  // A phase of exactly 1.0 reads entry 0, not table[len].  The single wrap of unroll_phase returns 1.0 for a phase in
+  // [-2^-54, 0) (phase + 1. rounds up), which osc_kernel can reach when |phase + incr| < 2^-54; the reference indexes past
+  // its table there and panics, so there is no behaviour to match.  The other two kernels fold ph >= 1 before they call.
+  const int prev_index = (int)floored >= len ? 0 : (int)floored;
   int next_index = prev_index + 1;
   if (next_index == len) next_index = 0;
   const float k = (float)(position - floored);
