@@ -391,6 +391,115 @@ NAMED = {
 }
 
 
+# ---- one small graph per planner branch that no graph above reaches (branches.txt) -----------------------------------------
+def g_frozen_fan_in(be):        # an oversampled WaveShaper that sums two sources: its codes come out of the dynamic-count rendering
+    c = _ctx(be)
+    sh = c.create_wave_shaper(curve=CURVE, oversample="2x")
+    _source(c).connect(sh)
+    _source(c, seed0=7).connect(sh)
+    sh.connect(c.destination())
+    return c
+
+
+def g_merger_falls_back(be):    # tests/test_channel_routing.py: both inputs of a merger in front of a panner stop mid-render
+    c = _ctx(be)
+    mg, pan = c.create_channel_merger(2), c.create_panner()
+    for k in range(2):
+        s = _source(c, n_ch=1, seed0=10 + k)
+        s.stop_at(0.05)
+        s.connect(mg, 0, k)
+    mg.connect(pan).connect(c.destination())
+    return c
+
+
+def g_mono_shaper_into_a_wide_downmix(be):
+    """a 5.1 source that ends early -> WaveShaper with curve(0) != 0 -> stereo destination (tests/test_wide_channels.py, fuzz seed
+    293): behind the source's end the shaper renders one channel where the static plan has six, into the 5.1 -> stereo matrix"""
+    c = _ctx(be)
+    _source(c, n_ch=6, frames=RQ * 20).connect(c.create_wave_shaper(curve=np.float32([0.5, 0.5, 0.5]))).connect(c.destination())
+    return c
+
+
+def g_bus_grows_input_by_input(be):
+    """stereo (ends early), mono and 5.1 into one bus: with the stereo source the mono one reaches 5.1 through stereo (L and R),
+    without it directly (C)"""
+    c = _ctx(be)
+    bus = c.create_gain(gain=0.7)
+    _source(c, n_ch=6, seed0=3).connect(bus)   # (summed in processing order: the source made last comes first)
+    _source(c, n_ch=1, seed0=2).connect(bus)
+    _source(c, n_ch=2, frames=RQ * 20, seed0=1).connect(bus)
+    bus.connect(c.destination())
+    return c
+
+
+def g_muted_cycle(be):          # tests/test_cycles.py: gain <-> gain without a DelayNode, the other source still renders
+    c = _ctx(be)
+    g1, g2 = c.create_gain(gain=0.5), c.create_gain(gain=0.5)
+    _source(c).connect(g1).connect(g2).connect(g1)
+    g2.connect(c.destination())
+    _source(c, seed0=3).connect(c.destination())
+    return c
+
+
+def g_short_echo_ring(be):      # 480 frames, shorter than a tile: planned for the ring kernel, and it qualifies
+    return _echo_loop(be, 0.01)
+
+
+def g_biquad_in_the_forward_transform(be):  # tests/test_plan.py: per-context coefficients cannot go into the one impulse response
+    ctx, nodes = t1(be, white_noise(3, 2, 480000), garage_like_ir(), device=waa.PLAN_ONLY, biquad_handle=True)
+    nodes["biquad"].frequency.set_value(300.0, instance=2)
+    return ctx
+
+
+def g_zero_gain_silent_modulator_refused(be):  # a gain of 0 whose modulator starts late: the reference emits the silent block
+    c = _ctx(be)
+    g = c.create_gain(gain=0.0)
+    lfo = c.create_oscillator(type_="sine", frequency=7.0)
+    lfo.connect(g.gain)
+    lfo.start_at(0.1)
+    _source(c).connect(g).connect(c.destination())
+    return c
+
+
+def g_mixed_buffer_widths(be):  # tests/test_dynamic_counts.py: mono, stereo and quad AudioBuffers on the three contexts
+    c = _ctx(be)
+    s = c.create_buffer_source()
+    for i, n_ch in enumerate((1, 2, 4)):
+        s.set_buffer(waa.AudioBuffer(white_noise(1, n_ch, c.length // 2 + 17 * i, seed0=70 + i)[0] * np.float32(0.5), SR), instance=i)
+    s.start_at(130.0 / SR)
+    s.connect(c.create_stereo_panner(pan=0.2)).connect(c.destination())
+    return c
+
+
+def g_short_loop_around_an_iir(be):
+    """tests/test_dynamic_counts.py: the static loop kernel does not cover an IIRFilter; its refusal plans the graph again with
+    the dynamic-count kernel"""
+    c = _ctx(be)
+    s = _source(c)
+    d = c.create_delay(0.05, delay_time=0.003)
+    f = c.create_iir_filter([0.2, 0.3, 0.1], [1.0, -0.5, 0.2])
+    s.connect(d)
+    d.connect(f).connect(c.create_gain(gain=0.5)).connect(d)
+    f.connect(c.destination())
+    return c
+
+
+# name -> (builder, measurement switches, what the branch writes into the text)
+BRANCHES = {
+    "frozen_fan_in": (g_frozen_fan_in, {}, "keeps frozen state over silent quanta and is not fed by a single source"),
+    "merger_falls_back": (g_merger_falls_back, {"WAA_STATIC_CHANNEL_COUNTS": "1"}, "comes from a ChannelMergerNode whose output falls back to one silent channel"),
+    "merger_falls_back_refused": (g_merger_falls_back, {}, "in a graph that needs exact per-quantum channel counts (dyn_kernel) is out of scope"),
+    "mono_shaper_into_a_wide_downmix": (g_mono_shaper_into_a_wide_downmix, {}, "with a rule that does not commute with the speakers up-mix made upstream"),
+    "bus_grows_input_by_input": (g_bus_grows_input_by_input, {}, "sums signals of different widths whose up-mixes depend on the order"),
+    "muted_cycle": (g_muted_cycle, {}, "is part of a cycle without a DelayNode: muted"),
+    "short_echo_ring": (g_short_echo_ring, {}, "(a feedback delay shorter than a tile: the ring kernel walks it in chunks shorter than the delay)"),
+    "biquad_in_the_forward_transform": (g_biquad_in_the_forward_transform, {}, "filtered by the forward transform's input stage"),
+    "zero_gain_silent_modulator_refused": (g_zero_gain_silent_modulator_refused, {}, "while the audio-rate input of the param is silent"),
+    "mixed_buffer_widths": (g_mixed_buffer_widths, {}, "dynamic-count group"),
+    "short_loop_around_an_iir": (g_short_loop_around_an_iir, {}, "dynamic-count group"),
+}
+
+
 def random_graph(seed, frozen):
     def build(be):
         c, _ = build_random_graph(be, seed, frozen=frozen)
@@ -463,6 +572,23 @@ def test_named_launch_lists_are_what_they_were(hip, monkeypatch):
     assert list(want) == list(NAMED)
     for name, (build, switches) in NAMED.items():
         got = describe(hip, build, switches, monkeypatch.setenv, monkeypatch.delenv)
+        assert got == want[name], name
+        assert "\nlaunch 0: " in got or (name.endswith("_refused") and got.startswith("refused with status 4:")), got
+
+
+def branches_text(be, setenv, delenv):
+    """branches.txt: like named.txt, for BRANCHES"""
+    return "".join(f"==== {name}\n{describe(be, build, switches, setenv, delenv)}" for name, (build, switches, _) in BRANCHES.items())
+
+
+def test_branch_launch_lists_are_what_they_were(hip, monkeypatch):
+    """the planner branches the named corpus does not reach, a graph each: the text says that the branch was taken, and is what
+    the planner wrote before build_plan_rest was split into passes"""
+    want = _sections(_golden("branches"))
+    assert list(want) == list(BRANCHES)
+    for name, (build, switches, phrase) in BRANCHES.items():
+        got = describe(hip, build, switches, monkeypatch.setenv, monkeypatch.delenv)
+        assert phrase in got, (name, got)
         assert got == want[name], name
         assert "\nlaunch 0: " in got or (name.endswith("_refused") and got.startswith("refused with status 4:")), got
 

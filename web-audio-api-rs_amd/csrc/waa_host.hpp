@@ -595,6 +595,17 @@ inline bool is_frozen_node(const Node& n) {
   return (n.desc.kind == WAA_NODE_WAVESHAPER && n.has_curve && n.desc.i[0] != WAA_OVERSAMPLE_NONE) ||
          (n.desc.kind == WAA_NODE_PANNER && n.desc.i[0] == WAA_PANNING_HRTF);
 }
+// nodes that go on rendering after their input has fallen silent (filter state, delay line, impulse response / HRIR tail)
+inline bool has_memory(const Node& n) {
+  const uint32_t k = n.desc.kind;
+  return k == WAA_NODE_BIQUAD || k == WAA_NODE_IIR_FILTER || k == WAA_NODE_DELAY || (k == WAA_NODE_CONVOLVER && n.has_ir) ||
+         (k == WAA_NODE_PANNER && n.desc.i[0] == WAA_PANNING_HRTF);
+}
+// what a WaveShaper's curve makes of a sample of 0 (waveshaper.rs:498-509); 0 without a curve
+inline float curve_at_zero(const Node& n) {
+  const size_t cn = n.curve.size();
+  return cn == 0 ? 0.f : (cn % 2 ? n.curve[cn / 2] : (n.curve[cn / 2 - 1] + n.curve[cn / 2]) / 2.f);
+}
 
 // internal node kind (never in a caller's graph): one connected output of a ChannelSplitterNode (waa_plan_route.cpp)
 constexpr uint32_t NODE_SPLITTER_PORT = 0x100u;

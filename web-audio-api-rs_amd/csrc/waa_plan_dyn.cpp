@@ -16,14 +16,12 @@
 namespace waa {
 namespace host {
 
-int plan_dynamic_groups(waa_batch* b, const DynPlanCtx& c) {
+int plan_dynamic_groups(waa_batch* b, const PlanPass& pass) {
   const uint32_t N = (uint32_t)b->nodes.size();
-  const std::vector<uint32_t>& items = c.items;
-  const std::vector<Unit>& units = c.units;
-  const std::vector<int>& scc_of = c.scc_of;
-  const auto& alloc_signal = c.alloc_signal;
-  const auto& plan_single = c.plan_single;
-  const bool count_change_found = c.count_change_found, mixed_buffer_counts = c.mixed_buffer_counts;
+  const std::vector<uint32_t>& items = pass.items;
+  const std::vector<Unit>& units = pass.units;
+  const std::vector<int>& scc_of = pass.scc_of;
+  const bool count_change_found = pass.count_change_found, mixed_buffer_counts = pass.mixed_buffer_counts;
   if (!count_change_found && mixed_buffer_counts)
     plan_note(b, "instances play AudioBuffers of different channel counts -> per-instance counts through dyn_kernel");
   else if (!count_change_found)
@@ -619,7 +617,7 @@ int plan_dynamic_groups(waa_batch* b, const DynPlanCtx& c) {
         const uint32_t vid = v & ~VTX_READER;
         Node& m = b->nodes[vid];
         if (!m.sig.base) {
-          int e = alloc_signal(m);
+          int e = alloc_signal(b, m);
           if (e) return e;
         }
         pending.push_back(v);
@@ -682,12 +680,12 @@ int plan_dynamic_groups(waa_batch* b, const DynPlanCtx& c) {
     const uint32_t id = unit.id;
     Node& n = b->nodes[id];
     if (unit.scc < 0 && is_src(n.desc.kind)) {
-      int e = alloc_signal(n);
+      int e = alloc_signal(b, n);
       if (e) return e;
       if (n.desc.kind == WAA_NODE_OSCILLATOR)
         e = plan_oscillator(b, id);
       else
-        e = plan_single(id);
+        e = plan_single(b, pass, id);
       if (e) return e;
       if ((e = source_codes(id))) return e;
       planned_node[id] = 1;
@@ -696,7 +694,7 @@ int plan_dynamic_groups(waa_batch* b, const DynPlanCtx& c) {
     for (uint32_t v : verts) {
       Node& m = b->nodes[v & ~VTX_READER];
       if (!m.sig.base) {
-        int e = alloc_signal(m);
+        int e = alloc_signal(b, m);
         if (e) return e;
       }
       if (std::find(pending.begin(), pending.end(), v) == pending.end()) pending.push_back(v);

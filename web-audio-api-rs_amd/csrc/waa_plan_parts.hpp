@@ -1,7 +1,11 @@
-// waa_plan_parts.hpp — what the parts of the planner share (waa_plan.cpp: order, liveness, chains, dynamic groups;
-// waa_plan_sources.cpp, waa_plan_loops.cpp, waa_plan_conv.cpp, waa_plan_ops.cpp, waa_plan_check.cpp).  Host only.
+// waa_plan_parts.hpp — what the parts of the planner share.  Host only.
+//   waa_plan.cpp         build_plan and its driver build_plan_rest, params, chains (plan_single / plan_chain), block-scheduled loops
+//   waa_plan_graph.cpp   processing order, feedback loops, edges in summing order, liveness, static channel counts, units
+//   waa_plan_counts.cpp  the replay of the reference's per-quantum silence and channel counts
+//   waa_plan_folds.cpp   frozen-node sources, folded delays, materialisation points, edge folds, source views, Biquad-into-Convolver
+//   waa_plan_dyn.cpp     dynamic-count groups;  waa_plan_loops.cpp  quantum-serial loops, delays;  waa_plan_sources.cpp, waa_plan_conv.cpp,
+//   waa_plan_comp.cpp, waa_plan_route.cpp, waa_plan_ops.cpp  the node kinds;  waa_plan_check.cpp  validation
 #pragma once
-#include <functional>
 #include <vector>
 
 #include "waa_host.hpp"
@@ -20,16 +24,45 @@ struct Unit {
   int scc;
   uint32_t id;
 };
-// what build_plan hands to the dynamic-group builder (waa_plan_dyn.cpp)
-struct DynPlanCtx {
-  const std::vector<uint32_t>& items;   // vertices in processing order (two per DelayNode)
-  const std::vector<Unit>& units;
-  const std::vector<int>& scc_of;
-  std::function<int(Node&)> alloc_signal;
-  std::function<int(uint32_t)> plan_single;
-  bool count_change_found, mixed_buffer_counts;
+// What the passes of build_plan hand each other (waa_plan.cpp: build_plan_rest lists them in order).  Everything else they
+// decide lives in the nodes (Node::in_edges / live / in_nch / materialized / delay_folded / is_view / fold_conv ...).
+struct PlanPass {
+  std::vector<uint32_t> items;  // compute_order: vertices in processing order (two per DelayNode)
+  std::vector<uint8_t> muted;   // compute_order: nodes of a cycle without a DelayNode
+  std::vector<int> scc_of;      // find_loops: feedback loop of a node, -1 outside loops
+  int n_scc = 0;
+  bool mixed_buffer_counts = false;  // static_channel_counts: instances play AudioBuffers of different widths
+  bool count_change_found = false;   // replay_channel_counts, choose_frozen_sources: the plan needs exact per-quantum counts
+  std::vector<int> frozen_src;       // choose_frozen_sources: the one source in front of a frozen-state node, or -1
+  std::vector<uint32_t> scc_block;   // choose_block_loops: tiles per block of a block-scheduled loop, 0 = quantum-serial
+  std::vector<uint8_t> mat_hard, fan_in_only;  // choose_materialisation: materialised for its own reasons / only for a summing consumer
+  std::vector<Unit> units;           // order_units
+  bool block_loop(uint32_t id) const { return scc_of[id] >= 0 && scc_block[(size_t)scc_of[id]] > 0; }
+  bool dynamic(const waa_batch* b) const { return count_change_found || b->force_dynamic; }
 };
-int plan_dynamic_groups(waa_batch* b, const DynPlanCtx& c);
+// waa_plan_graph.cpp
+void find_loops(const waa_batch* b, PlanPass& pass);                 // reads muted; writes scc_of, n_scc
+int collect_edges(waa_batch* b, const PlanPass& pass);              // reads muted, b->order; writes Node::in_edges / pin_edges / n_consumers, clears live / materialized
+void mark_live(waa_batch* b);                                        // reads the edges; writes Node::live
+int refuse_static_only_nodes(waa_batch* b, const PlanPass& pass, bool in_loops);  // live compressor / routing / per-instance-IR nodes
+int refuse_nested_source_modulation(const waa_batch* b);            // (prepass) reads Node::live
+int static_channel_counts(waa_batch* b, PlanPass& pass);            // writes Node::in_nch / out_nch, mixed_buffer_counts, b->force_dynamic
+void order_units(const waa_batch* b, PlanPass& pass);               // reads scc_of, the edges; writes units
+// waa_plan_counts.cpp
+int replay_channel_counts(waa_batch* b, PlanPass& pass);            // reads the edges, counts, schedules; writes count_change_found
+// waa_plan_folds.cpp (each reads what the ones above it wrote)
+void choose_frozen_sources(waa_batch* b, PlanPass& pass);           // writes frozen_src, count_change_found
+void choose_block_loops(waa_batch* b, PlanPass& pass);              // writes scc_block
+void choose_folded_delays(waa_batch* b, const PlanPass& pass);      // writes Node::delay_folded
+void choose_materialisation(waa_batch* b, PlanPass& pass);          // writes Node::materialized, mat_hard, fan_in_only
+void fold_fan_in_edges(waa_batch* b, const PlanPass& pass);         // clears Node::materialized of sources / gains that ride on an edge
+void choose_source_views(waa_batch* b, const PlanPass& pass);       // writes Node::is_view / view_sig / view_valid
+void fold_biquad_into_convolver(waa_batch* b, const PlanPass& pass);  // writes Node::fold_conv / pre_biquad
+// waa_plan.cpp
+int alloc_signal(waa_batch* b, Node& n);
+int plan_single(waa_batch* b, const PlanPass& pass, uint32_t id);   // one node outside a loop or of a block-scheduled loop, with the chain that ends in it
+// waa_plan_dyn.cpp
+int plan_dynamic_groups(waa_batch* b, const PlanPass& pass);
 // vertices of the expanded graph the cycle breaker works on: a DelayNode is two (writer `id`, reader `id | VTX_READER`)
 constexpr uint32_t VTX_READER = 0x80000000u;
 
@@ -49,7 +82,6 @@ int push_chain_step(waa_batch* b, const std::vector<InputRef>& inputs, int in_nc
 int temp_signal(waa_batch* b, int nch, SignalRef* out);
 int emit_segments(waa_batch* b, std::vector<InputRef> inputs, int in_nch, int in_interp, const std::vector<OpDesc>& ops, const SignalRef& out);
 bool is_delay(const waa_batch* b, uint32_t id);
-void vertex_targets(const waa_batch* b, uint32_t v, const std::vector<uint8_t>& cut, std::vector<uint32_t>& out);
 void vertex_targets(const waa_batch* b, uint32_t v, const std::vector<uint8_t>& cut, std::vector<uint32_t>& out);
 int materialise_automation(waa_batch* b);
 int source_code_rows(waa_batch* b, uint32_t id, uint64_t cs, std::vector<uint8_t>* out);
