@@ -308,7 +308,9 @@ waa_status waa_convolver_set_buffer(waa_batch* batch, uint32_t node, const float
 waa_status waa_waveshaper_set_curve(waa_batch* batch, uint32_t node, const float* curve, uint32_t n);
 /* OscillatorNode::set_periodic_wave(PeriodicWave::new(real, imag, disable_normalization))
  * (src/periodic_wave.rs:88-190, src/node/oscillator.rs:318-321): the 8192-point wavetable is generated on the
- * host; n >= 2 (IndexSizeError); real or imag may be NULL (zeros).  Switches the node to the custom type. */
+ * host; n >= 2 (IndexSizeError); real or imag may be NULL (zeros).  Switches the node to the custom type.  One wave per instance
+ * of the batch, its table generated on the device: waa_oscillator_set_periodic_wave_instance of include/waa_hip_device.h (the
+ * device library only). */
 waa_status waa_oscillator_set_periodic_wave(waa_batch* batch, uint32_t node, const float* real, const float* imag,
                                             uint32_t n, int32_t disable_normalization);
 /* The same, for a caller that already holds the finished PeriodicWave (the reference's render side: the processor receives

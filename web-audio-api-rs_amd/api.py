@@ -203,6 +203,9 @@ ABI = {
 # what include/waa_hip_device.h declares: entry points of the device library alone (the oracle keeps one context's worth of state)
 ABI_DEVICE = {
     "iir_set_coefficients_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _DP, C.c_uint32, _DP, C.c_uint32]),
+    "oscillator_set_periodic_wave_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, _FP, C.c_uint32, C.c_int32]),
+    "oscillator_set_wavetable_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, C.c_uint32]),
+    "oscillator_get_wavetable": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, C.c_uint32]),
 }
 
 
@@ -679,6 +682,7 @@ class OscillatorNode(_ScheduledSource):
         self.detune = AudioParam(self, 1, detune)
         self.params = [self.frequency, self.detune]
         self.periodic_wave = None
+        self._inst_waves = {}  # instance -> PeriodicWave: one wave per context (waa_oscillator_set_periodic_wave_instance)
         if periodic_wave is not None:
             self.set_periodic_wave(periodic_wave)
 
@@ -689,23 +693,83 @@ class OscillatorNode(_ScheduledSource):
             return
         self.type_ = type_
 
-    def set_periodic_wave(self, wave: PeriodicWave):
+    def set_periodic_wave(self, wave: PeriodicWave, instance: int = ALL):
+        """instance = ALL: the wave of every context without one of its own.  instance = i: context i's own PeriodicWave (coefficients
+        or PeriodicWave.from_wavetable); the node then works in per-instance mode, and the device library generates the tables of
+        the coefficient sets when the batch is planned.  Lengths may differ between contexts."""
+        if instance == ALL:
+            self.type_ = "custom"
+            self.periodic_wave = wave
+            return self
+        if self.context._handle is not None:
+            raise WaaError(3, "InvalidStateError - the batch is frozen once rendering has started")
+        if not 0 <= int(instance) < self.context.n_instances:
+            raise WaaError(1, f"instance {instance} out of range")
         self.type_ = "custom"
-        self.periodic_wave = wave
+        self._inst_waves[int(instance)] = wave
+        return self
+
+    def set_periodic_wave_batch(self, real, imag=None, disable_normalization: bool = False):
+        """real [n_instances, n] and / or imag [n_instances, n]: one PeriodicWave per context."""
+        r = None if real is None else _f32(real)
+        i = None if imag is None else _f32(imag)
+        n = self.context.n_instances
+        if (r is None and i is None) or any(a is not None and (a.ndim != 2 or a.shape[0] != n) for a in (r, i)):
+            raise WaaError(1, f"set_periodic_wave_batch takes [n_instances = {n}, n] arrays for real and / or imag, got "
+                              f"{None if r is None else r.shape} and {None if i is None else i.shape}")
+        for k in range(n):
+            self.set_periodic_wave(PeriodicWave(real=None if r is None else r[k], imag=None if i is None else i[k],
+                                                disable_normalization=disable_normalization), instance=k)
+        return self
+
+    @property
+    def per_instance(self) -> bool:
+        return bool(self._inst_waves)
+
+    def _check_per_instance(self):
+        if self.context._b.prefix != "waa_":
+            raise WaaError(4, "one PeriodicWave per instance is a feature of the device library; this binding keeps one wave "
+                              "per batch (render it one context at a time)")
+
+    def wavetable(self, instance: int = 0) -> np.ndarray:
+        """The 8192-point table context `instance` renders with.  A node in per-instance mode is planned first (which freezes the
+        batch): the answer is then the instance's row of the device's tables; otherwise, and on a plan-only context, the table
+        built on the host."""
+        self._check_per_instance()
+        if not 0 <= int(instance) < self.context.n_instances:
+            raise WaaError(1, f"instance {instance} out of range")
+        ctx = self.context
+        if self.per_instance:
+            ctx.plan_describe()
+        else:
+            ctx.prepare()
+        out = np.empty(8192, np.float32)
+        ctx._b.check(ctx._b.oscillator_get_wavetable(ctx._handle, self.id, int(instance), _fp(out), out.size))
+        return out
 
     def _fill_desc(self, d):
         d.i[0] = OSCILLATOR_TYPE[self.type_]
+        if self.per_instance:
+            self._check_per_instance()  # (refusals before the batch exists)
+
+    @staticmethod
+    def _set_wave(b, h, node, w, *inst):
+        if w.table is not None:
+            fn = b.oscillator_set_wavetable_instance if inst else b.oscillator_set_wavetable
+            b.check(fn(h, node, *inst, _fp(w.table), w.table.size))
+        else:
+            fn = b.oscillator_set_periodic_wave_instance if inst else b.oscillator_set_periodic_wave
+            b.check(fn(h, node, *inst, _fp(w.real), _fp(w.imag), w.real.size, int(w.disable_normalization)))
 
     def _apply(self, ctx):
         super()._apply(ctx)
+        b, h = ctx._b, ctx._handle
         if self.periodic_wave is not None:
-            w = self.periodic_wave
-            b, h = ctx._b, ctx._handle
-            if w.table is not None:
-                b.check(b.oscillator_set_wavetable(h, self.id, _fp(w.table), w.table.size))
-            else:
-                b.check(b.oscillator_set_periodic_wave(h, self.id, _fp(w.real), _fp(w.imag), w.real.size,
-                                                       int(w.disable_normalization)))
+            self._set_wave(b, h, self.id, self.periodic_wave)
+        if self.per_instance:
+            self._check_per_instance()
+            for i, w in sorted(self._inst_waves.items()):
+                self._set_wave(b, h, self.id, w, i)
 
 
 class BiquadFilterNode(AudioNode):

@@ -820,12 +820,8 @@ waa_status waa_waveshaper_set_curve(waa_batch* b, uint32_t node, const float* cu
   return WAA_OK;
 }
 
-// periodic_wave.rs:88-190 + oscillator.rs:318-321 (control side: the wavetable is generated on the host)
-waa_status waa_oscillator_set_periodic_wave(waa_batch* b, uint32_t node, const float* real, const float* imag, uint32_t nn,
-                                            int32_t disable_normalization) {
-  int e;
-  if ((e = check_node(b, node, WAA_NODE_OSCILLATOR)) || (e = check_unplanned(b))) return e;
-  if ((!real && !imag) || nn < 2) return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - `real` and `imag` length should at least 2");
+// the table of periodic_wave.rs:164-189 on the host: the shared wave's, and what the device's generator is held against
+static std::vector<float> host_periodic_wave_table(const float* real, const float* imag, uint32_t nn, bool disable_normalization) {
   const int size = 8192;
   std::vector<float> wavetable(size);
   const float pi_2 = 2.f * 3.14159265358979323846f;
@@ -849,7 +845,26 @@ waa_status waa_oscillator_set_periodic_wave(waa_batch* b, uint32_t node, const f
       for (float& v : wavetable) v *= norm_factor;
     }
   }
-  b->nodes[node].osc_wave.swap(wavetable);
+  return wavetable;
+}
+
+static int check_periodic_wave(const float* real, const float* imag, uint32_t nn) {
+  if ((!real && !imag) || nn < 2) return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - `real` and `imag` length should at least 2");
+  return 0;
+}
+static int check_wavetable(const float* table, uint32_t n) {
+  if (!table || n != WAA_PERIODIC_WAVE_TABLE_LENGTH)
+    return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - a PeriodicWave table has %d points (got %u)", WAA_PERIODIC_WAVE_TABLE_LENGTH, n);
+  return 0;
+}
+
+// periodic_wave.rs:88-190 + oscillator.rs:318-321 (control side: the wavetable is generated on the host)
+waa_status waa_oscillator_set_periodic_wave(waa_batch* b, uint32_t node, const float* real, const float* imag, uint32_t nn,
+                                            int32_t disable_normalization) {
+  int e;
+  if ((e = check_node(b, node, WAA_NODE_OSCILLATOR)) || (e = check_unplanned(b))) return e;
+  if ((e = check_periodic_wave(real, imag, nn))) return e;
+  host_periodic_wave_table(real, imag, nn, disable_normalization != 0).swap(b->nodes[node].osc_wave);
   return WAA_OK;
 }
 
@@ -857,9 +872,78 @@ waa_status waa_oscillator_set_periodic_wave(waa_batch* b, uint32_t node, const f
 waa_status waa_oscillator_set_wavetable(waa_batch* b, uint32_t node, const float* table, uint32_t n) {
   int e;
   if ((e = check_node(b, node, WAA_NODE_OSCILLATOR)) || (e = check_unplanned(b))) return e;
-  if (!table || n != WAA_PERIODIC_WAVE_TABLE_LENGTH)
-    return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - a PeriodicWave table has %d points (got %u)", WAA_PERIODIC_WAVE_TABLE_LENGTH, n);
+  if ((e = check_wavetable(table, n))) return e;
   b->nodes[node].osc_wave.assign(table, table + n);
+  return WAA_OK;
+}
+
+// every context of the reference builds its own PeriodicWave (periodic_wave.rs:88-190): one wave for one instance.  Only the
+// coefficients are kept here; plan_oscillator has the device generate the tables of the distinct sets (waa_periodic_wave.hip)
+static int osc_instance_slot(waa_batch* b, uint32_t node, uint32_t inst, Node::OscWave** slot) {
+  if (inst >= b->n_inst) return fail(WAA_ERR_INVALID_ARGUMENT, "instance %u out of range (OscillatorNode %u, %u instances)", inst, node, b->n_inst);
+  Node& n = b->nodes[node];
+  if (!n.per_inst_wave()) n.osc_inst.resize(b->n_inst);
+  *slot = &n.osc_inst[inst];
+  return 0;
+}
+
+waa_status waa_oscillator_set_periodic_wave_instance(waa_batch* b, uint32_t node, uint32_t inst, const float* real, const float* imag,
+                                                     uint32_t nn, int32_t disable_normalization) {
+  int e;
+  if ((e = check_node(b, node, WAA_NODE_OSCILLATOR)) || (e = check_unplanned(b))) return e;
+  if (inst == WAA_ALL_INSTANCES) return waa_oscillator_set_periodic_wave(b, node, real, imag, nn, disable_normalization);
+  if ((e = check_periodic_wave(real, imag, nn))) return e;
+  Node::OscWave* w = nullptr;
+  if ((e = osc_instance_slot(b, node, inst, &w))) return e;
+  w->table.clear();
+  w->real.assign(nn, 0.f);
+  w->imag.assign(nn, 0.f);
+  if (real) std::copy(real, real + nn, w->real.begin());
+  if (imag) std::copy(imag, imag + nn, w->imag.begin());
+  w->real[0] = w->imag[0] = 0.f;  // (entry 0 is never read, periodic_wave.rs:170: equal sets compare equal whatever it holds)
+  w->no_norm = disable_normalization != 0;
+  return WAA_OK;
+}
+
+waa_status waa_oscillator_set_wavetable_instance(waa_batch* b, uint32_t node, uint32_t inst, const float* table, uint32_t n) {
+  int e;
+  if ((e = check_node(b, node, WAA_NODE_OSCILLATOR)) || (e = check_unplanned(b))) return e;
+  if (inst == WAA_ALL_INSTANCES) return waa_oscillator_set_wavetable(b, node, table, n);
+  if ((e = check_wavetable(table, n))) return e;
+  Node::OscWave* w = nullptr;
+  if ((e = osc_instance_slot(b, node, inst, &w))) return e;
+  w->real.clear();
+  w->imag.clear();
+  w->table.assign(table, table + n);
+  return WAA_OK;
+}
+
+// the table an instance renders with: its row of the plan's tables once they exist, the host's table otherwise
+waa_status waa_oscillator_get_wavetable(waa_batch* b, uint32_t node, uint32_t inst, float* out, uint32_t n) {
+  int e;
+  if ((e = check_node(b, node, WAA_NODE_OSCILLATOR))) return e;
+  if (inst == WAA_ALL_INSTANCES) inst = 0;
+  if (inst >= b->n_inst) return fail(WAA_ERR_INVALID_ARGUMENT, "instance %u out of range (OscillatorNode %u, %u instances)", inst, node, b->n_inst);
+  if (!out || n != WAA_PERIODIC_WAVE_TABLE_LENGTH)
+    return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - a PeriodicWave table has %d points (got %u)", WAA_PERIODIC_WAVE_TABLE_LENGTH, n);
+  const Node& nd = b->nodes[node];
+  if (nd.per_inst_wave() && b->planned && !b->dry && nd.d_osc_tables) {
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));  // (the generator runs on the batch's stream)
+    uint32_t row = 0;
+    HIP_TRY(hipMemcpy(&row, nd.d_osc_row + inst, sizeof row, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, nd.d_osc_tables + (size_t)row * n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return WAA_OK;
+  }
+  const Node::OscWave* w = nd.per_inst_wave() && nd.osc_inst[inst].own() ? &nd.osc_inst[inst] : nullptr;
+  if (w && w->table.empty()) {
+    const std::vector<float> t = host_periodic_wave_table(w->real.data(), w->imag.data(), (uint32_t)w->real.size(), w->no_norm);
+    std::copy(t.begin(), t.end(), out);
+    return WAA_OK;
+  }
+  const std::vector<float>& t = w ? w->table : nd.osc_wave;
+  if (t.empty()) return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - oscillator %u has no PeriodicWave for instance %u", node, inst);
+  std::copy(t.begin(), t.end(), out);
   return WAA_OK;
 }
 

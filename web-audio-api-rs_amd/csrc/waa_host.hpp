@@ -171,6 +171,19 @@ struct Node {
   float* d_curve = nullptr;
   // oscillator: custom PeriodicWave table (8192 points, periodic_wave.rs:76)
   std::vector<float> osc_wave;
+  // one PeriodicWave per instance (waa_oscillator_set_periodic_wave_instance / _set_wavetable_instance): [n_inst] once the first
+  // instance has its own wave.  An instance holds coefficients (the plan generates its table on the device) or a finished table;
+  // one with neither uses osc_wave.  d_osc_tables / d_osc_row: the plan's [rows][8192] tables and the [n_inst] row index, made once
+  struct OscWave {
+    std::vector<float> real, imag, table;  // real / imag of equal length (a missing one is zeros), or the 8192-point table
+    bool no_norm = false;
+    bool own() const { return !real.empty() || !table.empty(); }
+  };
+  std::vector<OscWave> osc_inst;
+  bool per_inst_wave() const { return !osc_inst.empty(); }
+  float* d_osc_tables = nullptr;
+  uint32_t* d_osc_row = nullptr;
+  uint32_t osc_rows = 0, osc_gen_rows = 0;
   // iir filter: normalised coefficient pairs (iir_filter.rs:273-311)
   std::vector<double> iir_b, iir_a;
   // one set per instance (waa_iir_set_coefficients_instance): [n_inst] once the first instance has its own set, normalised like

@@ -417,6 +417,7 @@ struct OscDesc {
   const float* table;    // sine (2048 points) or the custom PeriodicWave (8192 points)
   int32_t table_len;
   int32_t type;          // WAA_OSC_*; sine and custom read `table`
+  const uint32_t* wave_row;  // non-null: one PeriodicWave per instance, `table` is [rows][table_len] and this the [n_inst] row index
   SignalRef out;         // 1 channel
   uint64_t frames;       // padded frames
   uint32_t n_inst;
@@ -439,6 +440,7 @@ struct OscDesc {
   const struct OscQuantum* fm_q;  // [rows][n_quanta] of the MODULATOR
   const uint32_t* fm_row;         // [n_inst] its row table
   const float* fm_table;
+  const uint32_t* fm_wave_row;    // the modulator's wave_row
   int32_t fm_table_len, fm_type;
   ParamRef fm_gain;               // mode 0 / 1 (fm_has_gain)
   int32_t fm_has_gain;
@@ -459,6 +461,21 @@ struct OscQuantum {
   int32_t outside_nyquist;
 };
 void launch_osc(const OscDesc& d, void* stream);
+
+// ---- PeriodicWave tables on the device (periodic_wave.rs:164-189; waa_periodic_wave.hip) --------------
+// One workgroup per distinct coefficient set: 8192 entries in the reference's f32 order, max |sample| through LDS, scaled by
+// 1 / max where the set asks for it.  Runs once at plan time (one table per context of a batch, plan_oscillator).
+constexpr int PERIODIC_WAVE_LEN = 8192;
+struct PeriodicWaveDesc {
+  const float* real;          // [rows][n], entry 0 unused
+  const float* imag;          // [rows][n]
+  const uint32_t* normalize;  // [rows] 1 = scale to a peak of 1
+  const uint32_t* dst_row;    // [rows] row of `tables` the set's table goes to
+  float* tables;              // [table rows][PERIODIC_WAVE_LEN]
+  uint32_t n;                 // padded coefficient count (>= 2)
+  uint32_t rows;
+};
+void launch_periodic_wave(const PeriodicWaveDesc& d, void* stream);
 
 // ---- feedback loops (graph.rs:323-487 cycle breaker): quantum-serial rendering of a strongly connected group ----
 // The members of a loop are rendered render quantum by render quantum, in the reference's processing order, by

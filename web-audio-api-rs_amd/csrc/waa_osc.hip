@@ -68,8 +68,9 @@ __device__ __forceinline__ float waveform_sample(int type, const float* table, i
     default: return table_sample(table, table_len, phase);  // sine (2048) or custom (8192)
   }
 }
-__device__ __forceinline__ float waveform_sample(const OscDesc& d, double phase, double phase_incr) {
-  return waveform_sample(d.type, d.table, d.table_len, phase, phase_incr);
+// the table an instance reads: the node's one table, or (one PeriodicWave per instance, OscDesc::wave_row) the instance's row
+__device__ __forceinline__ const float* table_of(const float* table, const uint32_t* wave_row, int table_len, uint32_t inst) {
+  return wave_row ? table + (uint64_t)wave_row[inst] * (uint64_t)table_len : table;
 }
 }  // namespace
 
@@ -103,6 +104,7 @@ __global__ __launch_bounds__(64) void osc_kernel(const OscDesc d) {
   if (inst >= d.n_inst) return;
   __builtin_amdgcn_s_setreg(1 | (6 << 6) | (1 << 11), 0);
   float* out = d.out.base + (uint64_t)inst * d.out.inst_stride;
+  const float* table = table_of(d.table, d.wave_row, d.table_len, inst);
   double start_time = d.start[inst];
   const double stop_time = d.stop[inst];
   const double sample_rate = d.sample_rate, dt = 1. / sample_rate, nyquist = sample_rate / 2.;
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(64) void osc_kernel(const OscDesc d) {
           }
           started = true;
         }
-        v = outside_nyquist ? 0.f : waveform_sample(d, phase, phase_incr);
+        v = outside_nyquist ? 0.f : waveform_sample(d.type, table, d.table_len, phase, phase_incr);
         phase = outside_nyquist ? unroll_phase_unbounded(phase + phase_incr) : unroll_phase(phase + phase_incr);
       }
       current_time += dt;
@@ -149,7 +151,7 @@ __global__ __launch_bounds__(64) void osc_kernel(const OscDesc d) {
           float r[4];
 #pragma unroll
           for (int e = 0; e < 4; e++) {
-            r[e] = waveform_sample(d, phase, phase_incr);
+            r[e] = waveform_sample(d.type, table, d.table_len, phase, phase_incr);
             phase = unroll_phase(phase + phase_incr);
           }
           o4[j] = make_float4(r[0], r[1], r[2], r[3]);
@@ -198,6 +200,7 @@ __global__ __launch_bounds__(256) void osc_par_kernel(const OscDesc d) {
   if (f0 >= d.frames) return;
   __builtin_amdgcn_s_setreg(1 | (6 << 6) | (1 << 11), 0);
   float* out = d.out.base + (uint64_t)inst * d.out.inst_stride;
+  const float* table = table_of(d.table, d.wave_row, d.table_len, inst);
   const uint32_t q = (uint32_t)(f0 / RQ);
   float r[4] = {0.f, 0.f, 0.f, 0.f};
   if (q < d.n_quanta) {
@@ -210,11 +213,49 @@ __global__ __launch_bounds__(256) void osc_par_kernel(const OscDesc d) {
         const double x = __builtin_fma((double)(i - oq.first), oq.incr, oq.phase);
         double ph = x - floor(x);
         if (ph >= 1.) ph -= 1.;
-        r[e] = waveform_sample(d, ph, oq.incr);
+        r[e] = waveform_sample(d.type, table, d.table_len, ph, oq.incr);
       }
     }
   }
   osc_store(d, inst, out, f0, r);
+}
+
+// The time-parallel kernel with one PeriodicWave per instance (OscDesc::wave_row): the same arithmetic, the instance's table staged
+// in LDS.  A workgroup of osc_par_kernel writes 4 KB and walks — at 220 Hz, 4.7 periods per 1024 frames — through all 32 KB of its
+// table: with ONE table per node that table stays in every cache, with 1024 of them every workgroup pulls its 32 KB through L2
+// again.  Here a workgroup stages the table once (8 x 16 B per lane) and renders OSC_LDS_SPAN x 1024 frames from it: 32 KB read per
+// 32 KB written.  32 KB of LDS per workgroup: 5 workgroups (20 wavefronts) per CU.
+constexpr int OSC_LDS_SPAN = 8;
+__global__ __launch_bounds__(256) void osc_par_lds_kernel(const OscDesc d) {
+  __shared__ float lds_table[PERIODIC_WAVE_LEN];
+  const uint32_t inst = blockIdx.y;
+  __builtin_amdgcn_s_setreg(1 | (6 << 6) | (1 << 11), 0);
+  const float4* src = reinterpret_cast<const float4*>(d.table + (uint64_t)d.wave_row[inst] * PERIODIC_WAVE_LEN);
+#pragma unroll
+  for (int k = 0; k < PERIODIC_WAVE_LEN / 4 / 256; k++) reinterpret_cast<float4*>(lds_table)[k * 256 + threadIdx.x] = src[k * 256 + threadIdx.x];
+  __syncthreads();
+  float* out = d.out.base + (uint64_t)inst * d.out.inst_stride;
+  for (int s = 0; s < OSC_LDS_SPAN; s++) {
+    const uint64_t f0 = (((uint64_t)blockIdx.x * OSC_LDS_SPAN + s) * 256 + threadIdx.x) * 4;
+    if (f0 >= d.frames) break;
+    const uint32_t q = (uint32_t)(f0 / RQ);
+    float r[4] = {0.f, 0.f, 0.f, 0.f};
+    if (q < d.n_quanta) {
+      const OscQuantum oq = d.table_q[(uint64_t)d.tq_row[inst] * d.n_quanta + q];
+      const int i0 = (int)(f0 % RQ);
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const int i = i0 + e;
+        if (i >= oq.first && i < oq.end && !oq.outside_nyquist) {
+          const double x = __builtin_fma((double)(i - oq.first), oq.incr, oq.phase);
+          double ph = x - floor(x);
+          if (ph >= 1.) ph -= 1.;
+          r[e] = table_sample(lds_table, PERIODIC_WAVE_LEN, ph);
+        }
+      }
+    }
+    osc_store(d, inst, out, f0, r);
+  }
 }
 
 // a-rate / graph-modulated frequency (FM): the phase is the running sum of per-frame increments.  One wavefront per
@@ -237,6 +278,8 @@ __global__ __launch_bounds__(64) void osc_scan_kernel(const OscDesc d) {
   const int lane = threadIdx.x;
   __builtin_amdgcn_s_setreg(1 | (6 << 6) | (1 << 11), 0);
   float* out = d.out.base + (uint64_t)inst * d.out.inst_stride;
+  const float* table = table_of(d.table, d.wave_row, d.table_len, inst);
+  const float* fm_table = table_of(d.fm_table, d.fm_wave_row, d.fm_table_len, inst);
   const int64_t first = d.active[(uint64_t)inst * 2], end = d.active[(uint64_t)inst * 2 + 1];
   const double ratio = d.start_ratio[inst];  // (time of frame `first` - start_time) / dt, 0 when it starts on a frame
   const double sample_rate = d.sample_rate, nyquist = sample_rate / 2.;
@@ -278,7 +321,7 @@ __global__ __launch_bounds__(64) void osc_scan_kernel(const OscDesc d) {
           const double x = __builtin_fma((double)(i - mq.first), mq.incr, mq.phase);
           double ph = x - floor(x);
           if (ph >= 1.) ph -= 1.;
-          m = waveform_sample(d.fm_type, d.fm_table, d.fm_table_len, ph, mq.incr);
+          m = waveform_sample(d.fm_type, fm_table, d.fm_table_len, ph, mq.incr);
         }
         if (d.fm_has_gain) {
           const float g = d.fm_gain.mode == 0 ? d.fm_gain.base[inst] : d.fm_gain.base[(uint64_t)inst * d.fm_gain.stride + q];
@@ -323,7 +366,7 @@ __global__ __launch_bounds__(64) void osc_scan_kernel(const OscDesc d) {
         if (f == first) p += incr[e] * ratio;
         p -= floor(p);
         if (p >= 1.) p -= 1.;
-        r[e] = (f >= first && f < end && !outside[e]) ? waveform_sample(d, p, incr[e]) : 0.f;
+        r[e] = (f >= first && f < end && !outside[e]) ? waveform_sample(d.type, table, d.table_len, p, incr[e]) : 0.f;
         ph += adv[e];
       }
       osc_store(d, inst, out, f0, r);
@@ -337,6 +380,11 @@ __global__ __launch_bounds__(64) void osc_scan_kernel(const OscDesc d) {
 
 void launch_osc(const OscDesc& d, void* stream) {
   if (d.table_q) {
+    if (d.wave_row && !measure_switch("WAA_OSC_NO_LDS_TABLE")) {  // (switch: the A/B of tools/periodic_wave_probe.py; the same bits)
+      const uint64_t span = 1024ull * OSC_LDS_SPAN;
+      hipLaunchKernelGGL(osc_par_lds_kernel, dim3((unsigned)((d.frames + span - 1) / span), d.n_inst), dim3(256), 0, (hipStream_t)stream, d);
+      return;
+    }
     hipLaunchKernelGGL(osc_par_kernel, dim3((unsigned)((d.frames + 1023) / 1024), d.n_inst), dim3(256), 0, (hipStream_t)stream, d);
     return;
   }

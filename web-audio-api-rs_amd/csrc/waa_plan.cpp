@@ -1367,6 +1367,13 @@ static int build_plan_impl(waa_batch* b) {
         if (n.iir_inst_b[inst].empty())
           return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - IIRFilterNode %u has no coefficients for instance %u", i, inst);
     }
+  for (uint32_t i = 0; i < N; i++) {  // one PeriodicWave per instance and no shared one: every instance needs its own
+    const Node& n = b->nodes[i];
+    if (n.desc.kind != WAA_NODE_OSCILLATOR || !n.per_inst_wave() || !n.osc_wave.empty()) continue;
+    for (uint32_t inst = 0; inst < b->n_inst; inst++)
+      if (!n.osc_inst[inst].own())
+        return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - OscillatorNode %u has no PeriodicWave for instance %u", i, inst);
+  }
   // processing order = reversed DFS post-order over outgoing edges in insertion order, cycle breakers applied
   // (graph.rs:323-487); `items` has two entries per DelayNode (writer, reader), none for muted nodes
   PlanPass pass;

@@ -300,6 +300,102 @@ static inline bool osc_quantum_fully_active(double block_time, double next_block
   return start_time <= block_time && stop_time >= next_block_time + dt;
 }
 
+// One PeriodicWave per instance (waa_oscillator_set_periodic_wave_instance): the node's tables are one device array
+// [rows][8192] with a row index per instance, like tq_row.  Instances with bitwise equal waves share a row: coefficient sets are
+// compared as the generator will see them (zero padded to the node's longest set, with the flag), finished tables — an
+// instance's own, or the shared wave's host-built one for an instance without a wave — as they are.  Finished tables are
+// uploaded into their rows; the rows of coefficient sets are generated by ONE launch of waa_periodic_wave.hip on the batch's
+// stream, here and not in the render's launch list: the tables depend on nothing a render or a re-arm changes.  They are made
+// once per batch (a second planning pass finds them in place).
+static int plan_periodic_wave_rows(waa_batch* b, uint32_t id) {
+  Node& n = b->nodes[id];
+  uint32_t n_max = 2;
+  for (uint32_t i = 0; i < b->n_inst; i++) {
+    const Node::OscWave& w = n.osc_inst[i];
+    if (!w.own() && n.osc_wave.empty()) return fail(WAA_ERR_INVALID_STATE, "internal: OscillatorNode %u, instance %u without a PeriodicWave got past build_plan", id, i);
+    n_max = std::max<uint32_t>(n_max, (uint32_t)w.real.size());
+  }
+  if (!n.d_osc_tables) {
+    PlanTrace trace("oscillator: per-instance PeriodicWave tables");
+    std::map<std::string, uint32_t> row_of_key;
+    std::vector<uint32_t> row_of(b->n_inst), gen_dst, gen_norm;
+    std::vector<float> gen_real, gen_imag;
+    std::vector<std::pair<uint32_t, const std::vector<float>*>> uploads;  // (row, finished table)
+    std::string key;
+    for (uint32_t i = 0; i < b->n_inst; i++) {
+      const Node::OscWave& w = n.osc_inst[i];
+      const bool coefs = !w.real.empty();
+      const std::vector<float>& table = w.own() ? w.table : n.osc_wave;
+      key.assign(1, coefs ? (w.no_norm ? 'u' : 'n') : 't');
+      if (coefs) {
+        key.append(reinterpret_cast<const char*>(w.real.data()), w.real.size() * sizeof(float));
+        key.append((size_t)(n_max - w.real.size()) * sizeof(float), '\0');
+        key.append(reinterpret_cast<const char*>(w.imag.data()), w.imag.size() * sizeof(float));
+        key.append((size_t)(n_max - w.imag.size()) * sizeof(float), '\0');
+      } else {
+        key.append(reinterpret_cast<const char*>(table.data()), table.size() * sizeof(float));
+      }
+      auto it = row_of_key.find(key);
+      if (it == row_of_key.end()) {
+        it = row_of_key.emplace(key, (uint32_t)row_of_key.size()).first;
+        if (coefs) {
+          gen_dst.push_back(it->second);
+          gen_norm.push_back(w.no_norm ? 0u : 1u);
+          gen_real.insert(gen_real.end(), w.real.begin(), w.real.end());
+          gen_real.resize((size_t)gen_dst.size() * n_max, 0.f);
+          gen_imag.insert(gen_imag.end(), w.imag.begin(), w.imag.end());
+          gen_imag.resize((size_t)gen_dst.size() * n_max, 0.f);
+        } else {
+          uploads.push_back({it->second, &table});
+        }
+      }
+      row_of[i] = it->second;
+    }
+    const uint32_t rows = (uint32_t)row_of_key.size();
+    float* d_tables = nullptr;
+    uint32_t* d_row = nullptr;
+    int e;
+    if ((e = dev_alloc(b, &d_tables, (size_t)rows * PERIODIC_WAVE_LEN, true)) || (e = dev_upload(b, &d_row, row_of))) return e;
+    for (const auto& up : uploads) {
+      float* dst = d_tables + (size_t)up.first * PERIODIC_WAVE_LEN;
+      if (b->dry)
+        std::memcpy(dst, up.second->data(), PERIODIC_WAVE_LEN * sizeof(float));
+      else
+        HIP_TRY(hipMemcpy(dst, up.second->data(), PERIODIC_WAVE_LEN * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (!uploads.empty() && !b->dry) HIP_TRY(hipStreamSynchronize(nullptr));  // (as in dev_upload: the rows are THERE)
+    if (!gen_dst.empty()) {
+      PeriodicWaveDesc pw{};
+      float *d_real = nullptr, *d_imag = nullptr;
+      uint32_t *d_norm = nullptr, *d_dst = nullptr;
+      if ((e = dev_upload(b, &d_real, gen_real)) || (e = dev_upload(b, &d_imag, gen_imag)) || (e = dev_upload(b, &d_norm, gen_norm)) ||
+          (e = dev_upload(b, &d_dst, gen_dst)))
+        return e;
+      pw.real = d_real;
+      pw.imag = d_imag;
+      pw.normalize = d_norm;
+      pw.dst_row = d_dst;
+      pw.tables = d_tables;
+      pw.n = n_max;
+      pw.rows = (uint32_t)gen_dst.size();
+      if (!b->dry) {  // (a plan-only batch has no device: its rows of coefficient sets stay unwritten)
+        // (WAA_PLAN_TRACE, measurement build: the kernel's own time, launch to idle — tools/periodic_wave_probe.py reads it)
+        PlanTrace kernel_trace("periodic_wave_kernel (launch to idle)");
+        launch_periodic_wave(pw, b->stream);
+        HIP_TRY(hipGetLastError());
+        if (kernel_trace.on) HIP_TRY(hipStreamSynchronize(b->stream));
+      }
+    }
+    n.d_osc_tables = d_tables;
+    n.d_osc_row = d_row;
+    n.osc_rows = rows;
+    n.osc_gen_rows = (uint32_t)gen_dst.size();
+  }
+  plan_note(b, "oscillator node %u: one PeriodicWave per instance: %u table row(s) for %u instance(s), %u generated on the device (coefficient sets padded to %u), %u uploaded",
+            id, n.osc_rows, b->n_inst, n.osc_gen_rows, n_max, n.osc_rows - n.osc_gen_rows);
+  return 0;
+}
+
 int plan_oscillator(waa_batch* b, uint32_t id) {
   // WAA_OSC_PLAN_CHECK=1 (tests): every quantum is walked frame by frame as before and the shortcut's answer is checked
   const bool check_replay = measure_switch("WAA_OSC_PLAN_CHECK") != nullptr;
@@ -321,21 +417,28 @@ int plan_oscillator(waa_batch* b, uint32_t id) {
   if ((e = dev_upload(b, &d_start, start)) || (e = dev_upload(b, &d_stop, stop))) return e;
   d.start = d_start;
   d.stop = d_stop;
-  d.type = n.osc_wave.empty() ? n.desc.i[0] : WAA_OSC_CUSTOM;
-  if (d.type == WAA_OSC_CUSTOM && n.osc_wave.empty())
+  d.type = n.osc_wave.empty() && !n.per_inst_wave() ? n.desc.i[0] : WAA_OSC_CUSTOM;
+  if (d.type == WAA_OSC_CUSTOM && n.osc_wave.empty() && !n.per_inst_wave())
     return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - custom oscillator %u has no PeriodicWave", id);
-  std::vector<float> table;
-  if (d.type == WAA_OSC_CUSTOM) {
-    table = n.osc_wave;
-  } else {  // oscillator.rs:16-28 (same libm sinf as the reference's f32::sin)
-    table.resize(2048);
-    const float pi = 3.14159265358979323846f;
-    for (int x = 0; x < 2048; x++) table[x] = std::sin(((float)x) * 2.0f * pi * (1.f / 2048.f));
+  if (n.per_inst_wave()) {
+    if ((e = plan_periodic_wave_rows(b, id))) return e;
+    d.table = n.d_osc_tables;
+    d.wave_row = n.d_osc_row;
+    d.table_len = PERIODIC_WAVE_LEN;
+  } else {
+    std::vector<float> table;
+    if (d.type == WAA_OSC_CUSTOM) {
+      table = n.osc_wave;
+    } else {  // oscillator.rs:16-28 (same libm sinf as the reference's f32::sin)
+      table.resize(2048);
+      const float pi = 3.14159265358979323846f;
+      for (int x = 0; x < 2048; x++) table[x] = std::sin(((float)x) * 2.0f * pi * (1.f / 2048.f));
+    }
+    float* d_table = nullptr;
+    if ((e = dev_upload(b, &d_table, table))) return e;
+    d.table = d_table;
+    d.table_len = (int32_t)table.size();
   }
-  float* d_table = nullptr;
-  if ((e = dev_upload(b, &d_table, table))) return e;
-  d.table = d_table;
-  d.table_len = (int32_t)table.size();
   d.out = n.sig;
   d.frames = b->lp;
   d.n_inst = b->n_inst;
@@ -565,6 +668,7 @@ void fuse_fm_operators(waa_batch* b) {
     d.fm_q = ms.osc.table_q;
     d.fm_row = ms.osc.tq_row;
     d.fm_table = ms.osc.table;
+    d.fm_wave_row = ms.osc.wave_row;  // (a modulator with one PeriodicWave per instance: the carrier looks its row up like the modulator would)
     d.fm_table_len = ms.osc.table_len;
     d.fm_type = ms.osc.type;
     d.fm_has_gain = ch.in[0].has_gain ? 1 : 0;

@@ -7,9 +7,9 @@ step for the Python mirror (round-5 review, missing 4): contexts built one by on
 (`OfflineAudioContext(channels, length, rate)` with n_instances = 1), are bucketed by `shape_key` — the graph (node kinds, options,
 channel configuration, connections), the context's format, the SHAPES of per-context payloads (an AudioBufferSource's channel count,
 length and rate, and on the device library the padded length of an IIRFilterNode's coefficients, which become per-instance sets of the
-batch) and the identity of payloads a batch shares (a convolver's impulse response, a shaper's curve, a periodic wave, IIR
-coefficients on other bindings) — every bucket is merged into one batch (per-context AudioBuffers, AudioParam values and automation, start / stop /
-loop settings become per-instance settings of the batch), rendered, and the AudioBuffers are handed back in the callers' order.
+batch) and the identity of payloads a batch shares (a convolver's impulse response, a shaper's curve, and on other bindings
+IIR coefficients and an oscillator's PeriodicWave, which the device library takes per instance) — every bucket is merged into one
+batch (per-context AudioBuffers, AudioParam values and automation, start / stop / loop settings become per-instance settings of the batch), rendered, and the AudioBuffers are handed back in the callers' order.
 Contexts with suspend callbacks render on their own (their callbacks may do anything)."""
 from __future__ import annotations
 
@@ -32,6 +32,15 @@ def _iir_set(nd):
     return nd._inst_coefs.get(0, (nd.feedforward, nd.feedback))
 
 
+def _osc_wave(nd):
+    """the PeriodicWave context 0 of an OscillatorNode renders with (None: a built-in waveform)"""
+    return nd._inst_waves.get(0, nd.periodic_wave)
+
+
+def _wave_id(w) -> tuple:
+    return ("table", _digest(w.table)) if w.table is not None else (_digest(w.real), _digest(w.imag), w.disable_normalization)
+
+
 def _node_key(nd) -> tuple:
     d = nd._desc()
     key = [type(nd).__name__, int(d.kind), int(d.channel_count), int(d.channel_count_mode), int(d.channel_interpretation),
@@ -51,9 +60,12 @@ def _node_key(nd) -> tuple:
             key.append(("iir-len", max(ff.size, fb.size)))
         else:
             key.append((_digest(ff), _digest(fb)))
-    if isinstance(nd, OscillatorNode) and nd.periodic_wave is not None:
-        w = nd.periodic_wave
-        key.append(_digest(w.table) if w.table is not None else (_digest(w.real), _digest(w.imag), w.disable_normalization))
+    if isinstance(nd, OscillatorNode) and _osc_wave(nd) is not None:
+        if nd.context._b.prefix == "waa_":
+            # the device library takes one PeriodicWave per context: contexts that differ only in their waves share a batch
+            key.append("periodic-wave")
+        else:
+            key.append(_wave_id(_osc_wave(nd)))
     if isinstance(nd, AudioBufferSourceNode):
         # per-context payloads: their SHAPE is part of the batch's shape (one device buffer [instance][channel][frame])
         if nd._batch is not None or nd._pcm is not None or nd._pcm_one or nd._device is not None:
@@ -125,6 +137,15 @@ def _merge(bucket: Sequence[OfflineAudioContext]) -> OfflineAudioContext:
             if not all(np.array_equal(ff, sets[0][0]) and np.array_equal(fb, sets[0][1]) for ff, fb in sets[1:]):
                 for i, (ff, fb) in enumerate(sets[1:], start=1):
                     cn.set_coefficients(ff, fb, instance=i)
+        if isinstance(cn, OscillatorNode) and _osc_wave(cn) is not None:
+            # every context's effective wave (_osc_wave) becomes its instance's; equal waves everywhere: the node stays shared
+            waves = [_osc_wave(nd) for nd in [cn] + others]
+            cn._inst_waves = {}
+            cn.periodic_wave = waves[0]
+            if not all(_wave_id(w) == _wave_id(waves[0]) for w in waves[1:]):
+                cn.periodic_wave = None  # (no shared wave: its table would be built on the host for nobody)
+                for i, w in enumerate(waves):
+                    cn.set_periodic_wave(w, instance=i)
         if isinstance(cn, AudioBufferSourceNode):
             if not all(o._buffers.get(ALL) is cn._buffers.get(ALL) for o in others):
                 if ALL in cn._buffers:
