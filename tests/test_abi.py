@@ -101,6 +101,96 @@ def test_context_construction_limits(be_plan):
     attempt(6, 129, 768000.0).close()
 
 
+def _graph(*nodes):
+    """a GraphDesc of node 0 = the destination and `nodes` = (kind, channel_count, channel_count_mode) behind it, no edges but
+    buffer source 1 -> destination; the arrays are returned too, to keep them alive"""
+    descs = (waa.api.NodeDesc * (1 + len(nodes)))()
+    descs[0].kind = waa.api.NODE_DESTINATION
+    for k, (kind, count, mode) in enumerate(nodes, 1):
+        descs[k].kind, descs[k].channel_count, descs[k].channel_count_mode = kind, count, mode
+    edges = (waa.api.EdgeDesc * 1)(waa.api.EdgeDesc(1, 0, 0, 0))
+    n_edges = 1 if nodes and nodes[0][0] == waa.api.NODE_BUFFER_SOURCE else 0
+    return waa.api.GraphDesc(len(descs), descs, n_edges, edges), descs, edges
+
+
+_FOUR_MAX = (4, waa.api.COUNT_MODE["max"])  # a channel count of 4 AND count mode max: which of the two a node reports first
+
+
+def _create(be, device, *nodes):
+    g, *_keep = _graph(*nodes)
+    h = ctypes.c_void_p()
+    status = be.batch_create(ctypes.byref(g), 1, 2, 128, 48000.0, device, ctypes.byref(h))
+    return status, h
+
+
+def _create_case(kind):
+    def run(be, device):
+        status, h = _create(be, device, (kind,) + _FOUR_MAX)
+        assert bool(h.value) == (status == 0)
+        if h.value:
+            be.batch_destroy(h)
+        return status
+    return run
+
+
+def _setter_case(call):
+    def run(be, device):
+        status, h = _create(be, device, (waa.api.NODE_BUFFER_SOURCE, 0, 0), (waa.api.NODE_CONVOLVER, 0, 0))
+        assert status == 0
+        try:
+            return call(be, h)
+        finally:
+            be.batch_destroy(h)
+    return run
+
+
+_PCM = (ctypes.c_int16 * 12)()
+
+
+def _source_buffer_on_planned_batch(be, h):
+    needed = ctypes.c_size_t()
+    be.check(be.plan_describe(h, None, 0, ctypes.byref(needed)))
+    plane = np.ones(4, np.float32)
+    ptrs = (waa.api._FP * 1)(plane.ctypes.data_as(waa.api._FP))
+    return be.source_set_buffer(h, 1, 5, ptrs, 1, 4, 48000.0)
+
+
+_PRECEDENCE_CASES = {
+    "create-stereo-panner": _create_case(waa.api.NODE_STEREO_PANNER),
+    "create-panner": _create_case(waa.api.NODE_PANNER),
+    "create-convolver": _create_case(waa.api.NODE_CONVOLVER),
+    "create-compressor": _create_case(waa.api.NODE_DYNAMICS_COMPRESSOR),
+    "source-pcm16-no-channels-low-rate": _setter_case(lambda be, h: be.source_set_buffer_pcm16(h, 1, 0, _PCM, 0, 4, 1000.0)),
+    "convolver-pcm16-three-channels-low-rate": _setter_case(lambda be, h: be.convolver_set_buffer_pcm16(h, 2, _PCM, 3, 4, 1000.0)),
+    "source-buffer-bad-instance-planned": _setter_case(_source_buffer_on_planned_batch),
+}
+# (status, message) per case: the same on the oracle and on the product unless a pair (oracle, product) says otherwise
+_PRECEDENCE_EXPECTED = {
+    "create-stereo-panner": (2, "NotSupportedError - StereoPannerNode channel count mode cannot be set to max"),
+    "create-panner": (2, "NotSupportedError - PannerNode channel count mode cannot be set to max"),
+    "create-convolver": (2, "NotSupportedError - ConvolverNode channel count cannot be greater than two"),
+    # (the oracle has no DynamicsCompressorNode, tests hold the product's against the reference's own renders: it takes the node)
+    "create-compressor": ((0, None), (2, "NotSupportedError - DynamicsCompressorNode channel count cannot be greater than two")),
+    "source-pcm16-no-channels-low-rate": (2, "NotSupportedError - Invalid number of channels"),
+    "convolver-pcm16-three-channels-low-rate": (2, "NotSupportedError - the convolution buffer must consist of 1, 2 or 4 channels"),
+    "source-buffer-bad-instance-planned": (1, "instance out of range"),
+}
+
+
+@pytest.mark.parametrize("case", sorted(_PRECEDENCE_CASES))
+def test_validation_precedence(be_plan, case):
+    """An argument list that breaks TWO rules: which one is reported, with which status and the whole message.  Through the raw
+    binding with a hand-built GraphDesc (api.py refuses some of these before the library sees them)."""
+    be, kw = be_plan
+    status = _PRECEDENCE_CASES[case](be, kw.get("device", -1))
+    message = be.last_error().decode() if status else None  # (a call that succeeds leaves the last message alone)
+    print(f"{case} [{be.prefix}]: ({status}, {message!r})")
+    expected = _PRECEDENCE_EXPECTED[case]
+    if isinstance(expected[0], tuple):
+        expected = expected[0 if be.prefix == "orc_" else 1]
+    assert (status, message) == expected
+
+
 def test_host_helpers_match_oracle(hip, orc):
     """Control-side helpers of the product (resample, frequency response) against the oracle."""
     rng = np.random.default_rng(5)

@@ -164,7 +164,7 @@ def test_parity_filter_sweep_and_flanger(hip, orc):
 
 # ---- playbackRate / detune of an AudioBufferSourceNode modulated from the graph (k-rate params: param.rs:739-760,
 # audio_buffer_source.rs:176-197).  The host replays the playhead, so the library renders the modulating subgraph at plan
-# time and reads one value per render quantum back (waa_abi.cpp::resolve_source_rate_modulation).
+# time and reads one value per render quantum back (waa_plan_prepass.cpp::resolve_source_rate_modulation).
 def _ramp_buffer(frames, n_ch=1):
     t = np.arange(frames, dtype=np.float32)
     return np.stack([np.sin(t * (0.01 + 0.003 * c)) for c in range(n_ch)]).astype(np.float32)

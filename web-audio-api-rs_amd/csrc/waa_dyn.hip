@@ -766,7 +766,7 @@ __device__ __forceinline__ void dyn_body(const DynDesc& d) {
           // (round 6) blocks of several quanta: the reader in the EARLIER launch of this block has already rendered the block's
           // later quanta with the ring count it found at the block's start.  The count it should have seen is this one, one
           // quantum late (delay.rs:515-530: ring[0].number_of_channels() right now) — a change anywhere but in the block's last
-          // quantum invalidates the block: flagged, and the host renders the loop again one quantum per block (waa_abi.cpp).
+          // quantum invalidates the block: flagged, and the host renders the loop again one quantum per block (settle_loops).
           if (li.xstate && sn != ist[it * 4 + 0] && q + 1 < bq1 && bq1 - bq0 > 1) store_global(li.xstate + (uint64_t)d.n_inst * 2, 1);
           ist[it * 4 + 0] = sn;
           if (sn == 1) ist[it * 4 + 1] = (int)q;

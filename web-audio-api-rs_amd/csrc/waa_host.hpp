@@ -1,5 +1,5 @@
 // waa_host.hpp — host-side data model of libwaa_hip.so shared by the scheduler (waa_schedule.cpp), the planner
-// (waa_plan.cpp), the executor (waa_run.cpp) and the C ABI (waa_abi.cpp).  Not part of the public interface (include/waa_hip.h).
+// (waa_plan*.cpp), the executor (waa_run.cpp) and the C ABI (waa_abi*.cpp, waa_analyser_host.cpp).  Not part of the public interface (include/waa_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -138,6 +138,16 @@ struct DeviceBuffer {  // an AudioBuffer resident in HBM
   bool valid = false;
   uint32_t count() const { return nch_true ? nch_true : nch; }
 };
+inline DeviceBuffer device_buffer(float* base, uint64_t ch_stride, uint64_t frames, uint32_t nch, float sr) {
+  DeviceBuffer db;
+  db.base = base;
+  db.ch_stride = ch_stride;
+  db.frames = frames;
+  db.nch = nch;
+  db.sr = sr;
+  db.valid = true;
+  return db;
+}
 
 struct SourceSched {  // per instance scheduling parameters
   double start = DBL_MAX, stop = DBL_MAX, offset = 0, duration = DBL_MAX;
@@ -417,14 +427,14 @@ struct waa_batch {
   int device = 0;
   int n_cu = 256;  // compute units of the device (plan-only batches: an MI355X)
   hipStream_t stream = nullptr;
-  void* stage = nullptr;  // pinned staging block for transfers from / to PAGEABLE caller memory (waa_internal_xfer_h2d / waa_internal_xfer_d2h, waa_abi.cpp)
+  void* stage = nullptr;  // pinned staging block for transfers from / to PAGEABLE caller memory (xfer_h2d / xfer_d2h, waa_xfer.cpp)
   std::vector<Node> nodes;
   std::vector<waa_edge_desc> edges;
   // OfflineAudioContext::suspend_sync (offline.rs:359-397): the control clock — the render quantum in front of which the render
   // is "suspended" (waa_render_range moves it); control calls made at ctl_q > 0 take effect from that quantum on.  An edge is
   // live for quanta [edge_on, edge_off): waa_connect / waa_disconnect at ctl_q > 0 (EDGE_NEVER: no end).  At plan time an edge
   // that is not live for the whole render becomes a GainNode whose gain is 1 inside the window and 0 outside
-  // (desugar_timed_edges, waa_abi.cpp): gain.rs' two fast paths — pass-through and silence — are exactly "connected" and "not".
+  // (desugar_timed_edges, waa_plan_prepass.cpp): gain.rs' two fast paths — pass-through and silence — are exactly "connected" and "not".
   uint32_t ctl_q = 0;
   std::vector<uint32_t> edge_on, edge_off;
   bool ranged = false;              // waa_render_range has been called: waa_render would render from the start again
@@ -457,7 +467,7 @@ struct waa_batch {
   // Graph-modulated playbackRate / detune of AudioBufferSourceNodes (k-rate params the HOST needs: the playhead replay).
   // prepass = true: build_plan plans only what feeds those params (the modulators and the params' summing chains); the steps
   // are run, one value per quantum is read back and installed as k-rate value blocks, the param edges are removed and the
-  // real plan is built (waa_abi.cpp::resolve_source_rate_modulation).
+  // real plan is built (waa_plan_prepass.cpp::resolve_source_rate_modulation).
   bool prepass = false;
   std::vector<std::pair<uint32_t, uint32_t>> prepass_params;  // (source node, param)
   std::vector<waa::ParamRef> prepass_refs;                          // per entry: the per-frame values the summing chain writes
@@ -469,7 +479,7 @@ struct waa_batch {
   uint64_t code_stride = 0;          // bytes per instance of a code table (n_quanta rounded up)
   bool rendered = false;
   // waa_render_sharded: buffers of the streamed source are allocated and registered first (the plan only needs their shape), filled
-  // from the host when the sub-batch has its turn on the link (fill_pending_uploads, waa_abi.cpp)
+  // from the host when the sub-batch has its turn on the link (fill_pending_uploads, waa_xfer.cpp)
   bool defer_fill = false;
   struct PendingFill {
     int kind;  // 0: f32 planes, 1: interleaved 16-bit PCM through the decode kernel
@@ -523,7 +533,7 @@ struct PlanTrace {
 // before anything else fragments the device's memory — from which the big buffers of every batch are carved in 2 MB-aligned
 // pieces; the slab is one mapping with the largest page-table fragments the driver gives, so WHERE a batch's output lands no
 // longer changes from batch to batch (the same kernel ran at 1.33 or 1.55 ms depending on the
-// hipMalloc that happened to serve its output).  Defined in waa_abi.cpp.
+// hipMalloc that happened to serve its output).  Defined in waa_arena.cpp.
 void* arena_alloc(int device, size_t bytes, bool read_only = false);  // (read_only: the top end of a graded arena)
 bool arena_free(int device, void* p);
 void* guard_alloc(int device, size_t bytes);  // WAA_GUARD_ALLOC=1 (testing aid, waa_arena.cpp)
@@ -644,6 +654,18 @@ inline int check_unplanned(waa_batch* b) {
   if (b->planned) return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - the batch is frozen once rendering has started");
   return 0;
 }
+inline int check_channel_count(uint32_t n_ch) {
+  if (n_ch == 0 || n_ch > WAA_MAX_CHANNELS) return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - Invalid number of channels");
+  return 0;
+}
+inline int check_sample_rate(float sr) {  // MIN/MAX_SAMPLE_RATE, src/lib.rs:149-160
+  if (!(sr >= 3000.f && sr <= 768000.f)) return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - Invalid sample rate: %f", sr);
+  return 0;
+}
+// the instances [lo, hi) a call names: one, or all `n` of them (WAA_ALL_INSTANCES)
+struct InstRange { uint32_t lo, hi; };
+inline InstRange inst_range(uint32_t inst, uint32_t n) { return inst == WAA_ALL_INSTANCES ? InstRange{0, n} : InstRange{inst, inst + 1}; }
+inline void set_bufs(Node& n, InstRange r, const DeviceBuffer& db) { std::fill(n.bufs.begin() + r.lo, n.bufs.begin() + r.hi, db); }
 
 }  // namespace host
 }  // namespace waa
@@ -677,8 +699,21 @@ std::vector<float> param_per_quantum(const waa_batch* b, const ParamStore& p, ui
 
 // ---- waa_plan.cpp: graph -> launch plan -----------------------------------------------------------------
 int build_plan(waa_batch* b);
+// waa_plan_prepass.cpp: what waa_render / waa_plan_describe call — the two pre-passes (one renders: never on a plan-only batch), then build_plan
+int plan_batch(waa_batch* b);
+// ... and, for everything that hands out results: waits for a render of optimistic multi-quantum loop blocks and repeats it if flagged
+int settle_loops(waa_batch* b);
 // waa_run.cpp: the launches of the current plan, from the initial state
 int run_steps(waa_batch* b);
+// ---- waa_xfer.cpp: transfers between CALLER memory and the device, through the batch's pinned staging block if pageable ----
+// `height` rows of `width` bytes, pitches in bytes; asynchronous on the batch's stream for pinned memory, complete on return otherwise
+int xfer_h2d(waa_batch* b, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height);
+int xfer_d2h(waa_batch* b, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height);
+int fill_upload(waa_batch* b, const waa_batch::PendingFill& f);
+int fill_pending_uploads(waa_batch* b);
+// waa_abi_sources.cpp: 16-bit PCM -> `planes` = [n_items][n_ch][stride] at the batch's rate (sources and the convolver's response)
+int decode_pcm16(waa_batch* b, const int16_t* pcm, uint32_t n_items, uint32_t n_ch, uint64_t frames, float src_sr, float** planes,
+                 uint64_t* stride_out, uint64_t* target_out);
 // waa_frozen_host.cpp: WaveShaper 2x / 4x and the HRTF panner as node-major steps; src_id >= 0: static plan, the node's
 // only input is that source node (its host-known codes stand in for the codes a dynamic plan computes on the device)
 int plan_oversampler(waa_batch* b, uint32_t id, int src_id);
@@ -686,6 +721,28 @@ int plan_hrtf(waa_batch* b, uint32_t id, int src_id);
 bool hrtf_sphere_loaded();
 void plan_note(waa_batch* b, const char* fmt, ...);
 int slot_for(waa_batch* b, const char* name);
+// one launch: the profiling events around it when the batch is profiled and the launch has a slot, the error check behind it
+template <typename L>
+int timed(waa_batch* b, int slot, L&& launch) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (b->profiling && slot >= 0) {
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, b->stream));
+  }
+  launch();
+  {
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess)
+      return fail(WAA_ERR_DEVICE, "launch of %s failed: %s", slot >= 0 ? b->prof[slot].name.c_str() : "a kernel without a profile slot",
+                  hipGetErrorString(le));
+  }
+  if (b->profiling && slot >= 0) {
+    HIP_TRY(hipEventRecord(e1, b->stream));
+    b->prof[slot].pending.push_back({e0, e1});
+  }
+  return 0;
+}
 void default_channel_config(Node& n, uint32_t n_out);
 void compute_order(const waa_batch* b, std::vector<uint8_t>* cut, std::vector<uint8_t>* muted, std::vector<uint32_t>* items);
 int computed_in_nch(const Node& n, int maxc);  // quantum.rs:543-547

@@ -92,7 +92,7 @@ int upload_param(waa_batch* b, const ParamStore& p, ParamRef* ref) {
       std::fill(host.begin() + (size_t)i * per, host.begin() + (size_t)(i + 1) * per, c);
     }
     for (auto& blk : p.blocks) {
-      uint32_t lo = blk.inst == WAA_ALL_INSTANCES ? 0 : blk.inst, hi = blk.inst == WAA_ALL_INSTANCES ? rows : blk.inst + 1;
+      const auto [lo, hi] = inst_range(blk.inst, rows);
       for (uint32_t i = lo; i < hi; i++)
         for (uint32_t k = 0; k < blk.nq; k++) {
           uint64_t q = blk.q0 + k;

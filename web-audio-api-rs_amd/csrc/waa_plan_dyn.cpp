@@ -609,7 +609,7 @@ int plan_dynamic_groups(waa_batch* b, const PlanPass& pass) {
         // (what the delay does NOT bound: the reader's channel count follows the writer's input with ONE quantum of lag whatever the
         // delay time — ring[0].number_of_channels() — so a block is only right while that count stands still inside it.  It does
         // almost always (it moves when a source starts or ends and when the loop falls silent); the writer flags the blocks where it
-        // did not, and the render is repeated one quantum per block: waa_abi.cpp::settle_loops.)
+        // did not, and the render is repeated one quantum per block: waa_plan_prepass.cpp::settle_loops.)
         if (measure_switch("WAA_LOOP_ONE_QUANTUM")) bq = 1;  // (A/B: the round-5 form)
         b->qgroup_quanta.back() = std::max(bq, 1u);
       }

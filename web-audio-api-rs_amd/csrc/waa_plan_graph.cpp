@@ -181,7 +181,7 @@ int collect_edges(waa_batch* b, const PlanPass& pass) {
       if (pid >= to.params.size()) return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - node %u has no param %u", ed.to, pid);
       const uint32_t k = to.desc.kind;
       const bool source_rate = k == WAA_NODE_BUFFER_SOURCE && (pid == WAA_PARAM_SOURCE_PLAYBACK_RATE || pid == WAA_PARAM_SOURCE_DETUNE);
-      if (source_rate && !b->prepass)  // (with a device these edges are resolved before the plan is built, waa_abi.cpp)
+      if (source_rate && !b->prepass)  // (with a device these edges are resolved before the plan is built, waa_plan_prepass.cpp)
         return fail(WAA_ERR_OUT_OF_SCOPE,
                     "playbackRate / detune of source node %u are modulated from the graph: the modulator is rendered at plan time, "
                     "which needs the device (plan-only batch)", ed.to);

@@ -1,33 +1,9 @@
 // waa_run.cpp — the executor: the launches of a finished plan (waa_batch::steps), in order, on the batch's stream.  One switch
-// over StepKind per range form (tiles, render quanta); feedback loops block by block (moved out of waa_abi.cpp, whose
-// waa_render / waa_settle_loops call run_steps).
+// over StepKind per range form (tiles, render quanta); feedback loops block by block.
 #include "waa_host.hpp"
 
 using namespace waa;
 using namespace waa::host;
-
-// one launch: the profiling events around it when the batch is profiled and the launch has a slot, the error check behind it
-template <typename L>
-static int timed(waa_batch* b, int slot, L&& launch) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (b->profiling && slot >= 0) {
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, b->stream));
-  }
-  launch();
-  {
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess)
-      return fail(WAA_ERR_DEVICE, "launch of %s failed: %s", slot >= 0 ? b->prof[slot].name.c_str() : "a kernel without a profile slot",
-                  hipGetErrorString(le));
-  }
-  if (b->profiling && slot >= 0) {
-    HIP_TRY(hipEventRecord(e1, b->stream));
-    b->prof[slot].pending.push_back({e0, e1});
-  }
-  return 0;
-}
 
 // the three shapes nearly every kind has: the descriptor as it stands, or a copy with its tile / quantum range set
 template <typename D>

@@ -19,15 +19,6 @@
 #include <map>
 
 #include "waa_host.hpp"
-extern "C" int waa_internal_xfer_d2h(waa_batch* b, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height);  // waa_abi.cpp
-
-extern "C" int waa_settle_loops(waa_batch* b);  // waa_abi.cpp
-
-namespace waa {
-namespace host {
-int fill_pending_uploads(waa_batch* b);
-}
-}  // namespace waa
 
 namespace {
 
@@ -118,7 +109,7 @@ waa_status waa_download_all_pcm16(waa_batch* b, int16_t* dst) {
   if (!b->planned || !b->rendered) return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - nothing rendered yet");
   if (b->length == 0) return WAA_OK;
   HIP_TRY(hipSetDevice(b->device));
-  if (int es = waa_settle_loops(b)) return es;
+  if (int es = settle_loops(b)) return es;
   const size_t count = (size_t)b->n_inst * b->length * b->n_out;
   if (!b->pcm_out) {  // (the batch's size never changes; owned by the batch like every other buffer: the device arena serves it when reserved)
     int e = dev_alloc(b, &b->pcm_out, count, true);
@@ -137,7 +128,7 @@ waa_status waa_download_all_pcm16(waa_batch* b, int16_t* dst) {
   d.n_items = b->n_inst;
   waa::launch_pcm16_pack(d, b->stream);
   HIP_TRY(hipGetLastError());
-  if (int e = waa_internal_xfer_d2h(b, dst, count * sizeof(int16_t), b->pcm_out, count * sizeof(int16_t), count * sizeof(int16_t), 1)) return e;
+  if (int e = xfer_d2h(b, dst, count * sizeof(int16_t), b->pcm_out, count * sizeof(int16_t), count * sizeof(int16_t), 1)) return e;
   HIP_TRY(hipStreamSynchronize(b->stream));
   return WAA_OK;
 }
