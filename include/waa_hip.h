@@ -149,7 +149,8 @@ enum {
  *     ANALYSER    i[0] = fft_size, d[0] smoothing_time_constant, d[1] min_decibels, d[2] max_decibels
  *                 i[1] = series hop H in render quanta (0: one pull per render), i[2] = first pull quantum F >= 0: a whole
  *                 series of pulls at q_k = F + k H <= n_quanta through the analyser getters (see there)
- *     WAVESHAPER  i[0] = oversample
+ *     WAVESHAPER  i[0] = oversample; one curve for the whole batch (waa_waveshaper_set_curve) or, on the device library, one per
+ *                 instance (waa_waveshaper_set_curve_instance, waa_hip_device.h: oversample none only)
  *     CONVOLVER   i[0] = disable_normalization (0/1)
  *                 i[1] = 0: one impulse response for the whole batch; 1: one impulse response per instance — every
  *                 OfflineAudioContext of the reference owns its ConvolverNode and its buffer.  With i[1] = 1
@@ -469,8 +470,9 @@ typedef struct waa_sharded_job {
                                   * sub-batch is created anew) when the graph has an edge into an AudioParam: its plan may hold
                                   * values rendered from the sub-batch's own audio (waa_batch_rearm).  A `setup` that hands
                                   * every sub-batch its own slice [first, first + count) of per-instance impulse responses
-                                  * (CONVOLVER i[1] = 1) or of per-instance IIR coefficient sets
-                                  * (waa_iir_set_coefficients_instance, waa_hip_device.h) depends on `first`: leave this 0 there */
+                                  * (CONVOLVER i[1] = 1), of per-instance IIR coefficient sets or of per-instance WaveShaper curves
+                                  * (waa_iir_set_coefficients_instance, waa_waveshaper_set_curve_instance, waa_hip_device.h)
+                                  * depends on `first`: leave this 0 there */
 } waa_sharded_job;
 /* Blocks until every context is rendered and downloaded; *seconds (may be NULL) = wall time.  Pinned host buffers let
  * the transfers run at link speed, and a device arena (waa_device_arena_reserve, once per process) keeps hipMalloc / hipFree —

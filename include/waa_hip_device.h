@@ -61,6 +61,24 @@ waa_status waa_oscillator_set_wavetable_instance(waa_batch* batch, uint32_t node
  * finished table, or its coefficients through the host's generator.  InvalidStateError if the instance has no wave at all. */
 waa_status waa_oscillator_get_wavetable(waa_batch* batch, uint32_t node, uint32_t instance, float* out, uint32_t n);
 
+/* WaveShaperNode::set_curve of ONE context of the batch (src/node/waveshaper.rs:203-217): in the reference every context sets
+ * the curve of its own WaveShaperNode.  Replaces one batch, one plan and one launch sequence per distinct curve: a sweep over
+ * drive amounts, a thousand clips each through its own saturator, sound matching over distortion shapes.
+ *
+ * Refused once the batch is planned (InvalidStateError), for an instance >= n_instances, for a node of another kind and for a
+ * curve without points (WAA_ERR_INVALID_ARGUMENT); a second curve for the same instance is "InvalidStateError - cannot assign
+ * curve twice", as for the shared call.  instance = WAA_ALL_INSTANCES is waa_waveshaper_set_curve.  The first call with a real
+ * instance puts the node into per-instance mode; an instance without a curve of its own uses the shared one, and an instance
+ * that has neither renders as the reference renders a node without a curve: its input passes through.  That is no error.
+ *
+ * Lengths may differ between instances and nothing is padded: every instance keeps its own length, because the lookup's scale
+ * is (n - 1) / 2.  Instances with bitwise equal curves share one copy on the device.  Such a node ends its chain: its input is
+ * a materialised signal (or a source read in place) and one launch of its own renders it; what it computes
+ * per sample is the expression the shared curve is rendered with, bit for bit.  Out of scope (status 4, naming the node): the
+ * node inside a feedback loop, in a graph that needs exact per-quantum channel counts, and with oversample 2x / 4x.
+ * waa_batch_rearm keeps the curves, like everything but the audio. */
+waa_status waa_waveshaper_set_curve_instance(waa_batch* batch, uint32_t node, uint32_t instance, const float* curve, uint32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,7 @@ ABI_DEVICE = {
     "oscillator_set_periodic_wave_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, _FP, C.c_uint32, C.c_int32]),
     "oscillator_set_wavetable_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, C.c_uint32]),
     "oscillator_get_wavetable": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, C.c_uint32]),
+    "waveshaper_set_curve_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, C.c_uint32]),
 }
 
 
@@ -1162,31 +1163,73 @@ class AnalyserNode(AudioNode):
 
 
 class WaveShaperNode(AudioNode):
+    """src/node/waveshaper.rs:139-253.  A context of the batch may be given its own curve before the render (every context of
+    the reference sets the curve of its own node)."""
+
     kind = NODE_WAVESHAPER
 
     def __init__(self, ctx, curve=None, oversample="none", **kw):
         super().__init__(ctx, **kw)
         self.oversample = oversample
         self.curve = None
+        self._inst_curves = {}  # instance -> curve: one curve per context (waa_waveshaper_set_curve_instance)
         if curve is not None:
             self.set_curve(curve)
 
-    def set_curve(self, curve):
-        if self.curve is not None:
+    def set_curve(self, curve, instance: int = ALL):
+        """instance = ALL: the curve of every context without one of its own.  instance = i: context i's own curve; the node then
+        works in per-instance mode.  Lengths may differ between contexts; a context that has neither passes its input through."""
+        if instance == ALL:
+            if self.curve is not None:
+                raise WaaError(3, "InvalidStateError - cannot assign curve twice")
+            self.curve = _f32(curve)
+            return self
+        if self.context._handle is not None:
+            raise WaaError(3, "InvalidStateError - the batch is frozen once rendering has started")
+        if not 0 <= int(instance) < self.context.n_instances:
+            raise WaaError(1, f"instance {instance} out of range")
+        if int(instance) in self._inst_curves:
             raise WaaError(3, "InvalidStateError - cannot assign curve twice")
-        self.curve = _f32(curve)
+        own = _f32(curve).reshape(-1)
+        if own.size == 0:
+            raise WaaError(1, "a curve of its own has at least one point")
+        self._inst_curves[int(instance)] = own
         return self
+
+    def set_curve_batch(self, curves):
+        """curves: a sequence of n_instances arrays, one curve per context, of possibly different lengths"""
+        n = self.context.n_instances
+        if len(curves) != n:
+            raise WaaError(1, f"set_curve_batch takes n_instances = {n} curves, got {len(curves)}")
+        for i, c in enumerate(curves):
+            self.set_curve(c, instance=i)
+        return self
+
+    @property
+    def per_instance(self) -> bool:
+        return bool(self._inst_curves)
+
+    def _check_per_instance(self):
+        if self.context._b.prefix != "waa_":
+            raise WaaError(4, "one curve per instance is a feature of the device library; this binding keeps one curve "
+                              "per batch (render it one context at a time)")
 
     def set_oversample(self, oversample: str):
         self.oversample = oversample
 
     def _fill_desc(self, d):
         d.i[0] = OVERSAMPLE[self.oversample]
+        if self.per_instance:
+            self._check_per_instance()  # (refusals before the batch exists)
 
     def _apply(self, ctx):
+        b, h = ctx._b, ctx._handle
         if self.curve is not None:
-            b, h = ctx._b, ctx._handle
             b.check(b.waveshaper_set_curve(h, self.id, _fp(self.curve), self.curve.size))
+        if self.per_instance:
+            self._check_per_instance()
+            for i, c in sorted(self._inst_curves.items()):
+                b.check(b.waveshaper_set_curve_instance(h, self.id, i, _fp(c), c.size))
 
 
 def _dp(a: np.ndarray):

@@ -109,6 +109,24 @@ waa_status waa_waveshaper_set_curve(waa_batch* b, uint32_t node, const float* cu
   return WAA_OK;
 }
 
+// every context of the reference constructs its own WaveShaperNode and sets its own curve (waveshaper.rs:203-217): one curve for one instance
+waa_status waa_waveshaper_set_curve_instance(waa_batch* b, uint32_t node, uint32_t inst, const float* curve, uint32_t nn) {
+  int e;
+  if ((e = check_node(b, node, WAA_NODE_WAVESHAPER)) || (e = check_unplanned(b))) return e;
+  if (inst == WAA_ALL_INSTANCES) return waa_waveshaper_set_curve(b, node, curve, nn);
+  if (inst >= b->n_inst) return fail(WAA_ERR_INVALID_ARGUMENT, "instance %u out of range (WaveShaperNode %u, %u instances)", inst, node, b->n_inst);
+  if (!curve || nn == 0) return fail(WAA_ERR_INVALID_ARGUMENT, "WaveShaperNode %u, instance %u: a curve of its own has at least one point", node, inst);
+  Node& n = b->nodes[node];
+  if (n.per_inst_curve() && n.curve_inst_set[inst]) return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - cannot assign curve twice");
+  if (!n.per_inst_curve()) {
+    n.curve_inst.resize(b->n_inst);
+    n.curve_inst_set.assign(b->n_inst, 0);
+  }
+  n.curve_inst[inst].assign(curve, curve + nn);
+  n.curve_inst_set[inst] = 1;
+  return WAA_OK;
+}
+
 // the table of periodic_wave.rs:164-189 on the host: the shared wave's, and what the device's generator is held against
 static std::vector<float> host_periodic_wave_table(const float* real, const float* imag, uint32_t nn, bool disable_normalization) {
   const int size = 8192;

@@ -179,6 +179,16 @@ struct Node {
   std::vector<float> curve;
   bool has_curve = false;
   float* d_curve = nullptr;
+  // one curve per instance (waa_waveshaper_set_curve_instance): [n_inst] once the first instance has its own curve; an instance
+  // whose flag is clear uses `curve` if the node has one (has_curve) and passes its input through otherwise
+  std::vector<std::vector<float>> curve_inst;
+  std::vector<uint8_t> curve_inst_set;
+  bool per_inst_curve() const { return !curve_inst_set.empty(); }
+  // the curve `inst` renders with; nullptr: none (waveshaper.rs:402: the input is copied)
+  const std::vector<float>* curve_of(uint32_t inst) const {
+    if (per_inst_curve() && curve_inst_set[inst]) return &curve_inst[inst];
+    return has_curve ? &curve : nullptr;
+  }
   // oscillator: custom PeriodicWave table (8192 points, periodic_wave.rs:76)
   std::vector<float> osc_wave;
   // one PeriodicWave per instance (waa_oscillator_set_periodic_wave_instance / _set_wavetable_instance): [n_inst] once the first
@@ -299,8 +309,9 @@ enum class StepKind : int {
   OsFft = 20,             // the oversampled WaveShaper in one launch (waa_osfft.hip)
   Compressor = 21,        // DynamicsCompressorNode: level, detector, apply (waa_compressor.hip)
   Route = 22,             // channel routing (route_kernel)
+  ShaperInst = 23,        // WaveShaperNode with one curve per instance (waa_shaper_inst.hip)
 };
-constexpr int N_STEP_KINDS = 23;
+constexpr int N_STEP_KINDS = 24;
 
 // The per-kind facts that the planner's loop handling, its fusions and the executor ask for, in one place.
 struct StepTraits {
@@ -309,8 +320,8 @@ struct StepTraits {
   bool quantum_ranged;  // can be launched over a range of render quanta: exactly the cases of run_step_q (waa_run.cpp)
   bool frozen_state;    // launch of a frozen-state node: refused inside a block-scheduled loop
   // the echo-tail fusion (waa_plan_loops.cpp) counts the readers of a delay line from step_io's read sets and leaves the whole plan
-  // alone when a launch is of a kind whose reads it takes as unknown.  ConvCodes and Link report none to step_io; Compressor and
-  // Route report theirs, but were added after the fusion and have not been tried with it.
+  // alone when a launch is of a kind whose reads it takes as unknown.  ConvCodes and Link report none to step_io; Compressor,
+  // Route and ShaperInst report theirs, but were added after the fusion and have not been tried with it.
   bool reads_unknown_to_echo_fusion;
 };
 inline const StepTraits& step_traits(StepKind k) {
@@ -339,6 +350,7 @@ inline const StepTraits& step_traits(StepKind k) {
       {"os_fft",              false, true,  true,  false},
       {"compressor",          false, false, false, true},
       {"route",               false, false, false, true},
+      {"shaper_inst",         false, false, false, true},
   };
   static_assert(sizeof traits / sizeof traits[0] == N_STEP_KINDS, "one row per StepKind, in the enum's order");
   return traits[(int)k];
@@ -367,6 +379,7 @@ struct Step {
   HrtfDesc hrtf{};
   RouteDesc route{};      // Route: ChannelMergerNode / the input bus of a ChannelSplitterNode (waa_route.hip; reads / writes in loop_reads / loop_writes)
   CompDesc comp{};        // Compressor (profile slots: slot_fwd = level, slot_mac = detector, slot_inv = apply)
+  ShaperInstDesc shaper{};  // ShaperInst
   int slot_fwd = -1, slot_mac = -1, slot_inv = -1;
   void* zero_ptr = nullptr;
   size_t zero_bytes = 0;
@@ -625,10 +638,11 @@ inline bool has_memory(const Node& n) {
          (k == WAA_NODE_PANNER && n.desc.i[0] == WAA_PANNING_HRTF);
 }
 // what a WaveShaper's curve makes of a sample of 0 (waveshaper.rs:498-509); 0 without a curve
-inline float curve_at_zero(const Node& n) {
-  const size_t cn = n.curve.size();
-  return cn == 0 ? 0.f : (cn % 2 ? n.curve[cn / 2] : (n.curve[cn / 2 - 1] + n.curve[cn / 2]) / 2.f);
+inline float curve_at_zero(const std::vector<float>& curve) {
+  const size_t cn = curve.size();
+  return cn == 0 ? 0.f : (cn % 2 ? curve[cn / 2] : (curve[cn / 2 - 1] + curve[cn / 2]) / 2.f);
 }
+inline float curve_at_zero(const Node& n) { return curve_at_zero(n.curve); }
 
 // internal node kind (never in a caller's graph): one connected output of a ChannelSplitterNode (waa_plan_route.cpp)
 constexpr uint32_t NODE_SPLITTER_PORT = 0x100u;
@@ -637,6 +651,9 @@ inline bool is_routing_node(const Node& n) {
 }
 // DynamicsCompressorNode: rendered node-major by launches of its own (waa_compressor.hip), input and output materialised
 inline bool is_compressor(const Node& n) { return n.desc.kind == WAA_NODE_DYNAMICS_COMPRESSOR; }
+// WaveShaperNode with one curve per instance: ends a chain like the compressor, rendered node-major by one launch of its own
+// (waa_shaper_inst.hip), input and output materialised; never folded into a neighbour's kernel, whose curve is one per launch
+inline bool is_shaper_per_instance(const Node& n) { return n.desc.kind == WAA_NODE_WAVESHAPER && n.per_inst_curve(); }
 // quanta of look-ahead, in f32 exactly as dynamics_compressor.rs:253-254 sizes its ring (ring - 1)
 inline uint32_t compressor_delay_quanta(float sample_rate) { return (uint32_t)std::ceil(sample_rate * 0.006f / (float)RQ); }
 

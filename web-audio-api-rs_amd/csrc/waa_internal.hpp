@@ -269,6 +269,29 @@ void launch_compressor_level(const CompDesc& d, void* stream);
 void launch_compressor_detector(const CompDesc& d, void* stream);
 void launch_compressor_apply(const CompDesc& d, void* stream);
 
+// ---- WaveShaperNode with one curve per instance (waa_waveshaper_set_curve_instance), node-major in one launch (waa_shaper_inst.hip) ----
+// The curves of a node are one pool of floats, one row per DISTINCT curve; a row starts on a 16-byte boundary and the pool is
+// padded to whole 16-byte groups, so that a row is staged with 16-byte loads.
+struct ShaperRow {
+  uint32_t offset, length;  // pool[offset .. offset + length): the instance's curve; length 0 = no curve, the instance passes through
+};
+// points of the longest curve the kernel stages in LDS (form A); one longer curve in a node and the whole launch reads its curves
+// from global memory (form B).  32 KB per workgroup: four workgroups = four wavefronts per SIMD fit the 160 KB of a CU.
+constexpr int SHAPER_LDS_CAP = 8192;
+constexpr int SHAPER_TILE = 4096;  // frames of a workgroup's time tile: the staged curve serves 16 KB per channel
+struct ShaperInstDesc {
+  SignalRef in;            // the node's mixed input
+  uint64_t in_valid;       // frames of `in` that may be read (zeros beyond: a source read in place)
+  SignalRef out;           // same channel count
+  const float* pool;
+  const ShaperRow* rows;   // [n_inst]
+  uint32_t n_inst, n_quanta;
+  uint64_t frames;         // padded frames per channel (a multiple of TILE)
+  int32_t nch;
+  uint32_t lds_floats;     // form A: floats of LDS per workgroup (the longest curve, in whole 16-byte groups); 0: form B
+};
+void launch_shaper_inst(const ShaperInstDesc& d, void* stream);
+
 // ---- ChannelSplitterNode / ChannelMergerNode (channel_splitter.rs:183-210, channel_merger.rs:145-172): waa_route.hip ----
 // Row r of the output is the sum, in connection order, of terms[row_off[r]] .. terms[row_off[r + 1] - 1]; a row without
 // terms is WRITTEN as zeros.  A term is one channel of a source signal or one of the speakers down-mixes to mono of

@@ -15,6 +15,7 @@
 
 #include <cstdlib>
 
+#include "waa_curve.hpp"
 #include "waa_internal.hpp"
 #include "waa_mix.hpp"
 
@@ -488,31 +489,7 @@ __device__ __forceinline__ void biquad_op(const OpDesc& op, uint32_t inst, uint3
   __syncthreads();
 }
 
-// waveshaper.rs:555-573
-__device__ __forceinline__ float apply_curve(const float* curve, int nn, float input) {
-  if (nn == 0) return 0.f;
-  const float n = (float)nn;
-  const float v = (n - 1.f) / 2.0f * (input + 1.f);
-  if (v <= 0.f) return curve[0];
-  if (v >= n - 1.f) return curve[nn - 1];
-  const float k = floorf(v);
-  const float f = v - k;
-  const int ki = (int)k;
-  return (1.f - f) * curve[ki] + f * curve[ki + 1];
-}
-
-// the same lookup on a curve staged in LDS
-__device__ __forceinline__ float apply_curve_lds(const __attribute__((address_space(3))) float* curve, int nn, float input) {
-  if (nn == 0) return 0.f;
-  const float n = (float)nn;
-  const float v = (n - 1.f) / 2.0f * (input + 1.f);
-  if (v <= 0.f) return curve[0];
-  if (v >= n - 1.f) return curve[nn - 1];
-  const float k = floorf(v);
-  const float f = v - k;
-  const int ki = (int)k;
-  return (1.f - f) * curve[ki] + f * curve[ki + 1];
-}
+// (the WaveShaper's curve lookup, apply_curve / apply_curve_lds: waa_curve.hpp, shared with waa_shaper_inst.hip)
 
 __device__ __forceinline__ void stereo_gains_dev(float x, float& gl, float& gr) {
   const float PI_F = 3.14159265358979323846f;

@@ -1144,6 +1144,10 @@ int plan_single(waa_batch* b, const PlanPass& pass, uint32_t id) {
     if (int e = alloc_signal(b, term)) return e;
     return plan_compressor(b, id);
   }
+  if (is_shaper_per_instance(term)) {
+    if (int e = alloc_signal(b, term)) return e;
+    return plan_shaper_per_instance(b, id);
+  }
   if (term.desc.kind == WAA_NODE_CHANNEL_SPLITTER) {
     bool producer_in_loop = false;
     for (int e : term.in_edges) producer_in_loop |= scc_of[b->edges[e].from] >= 0;
@@ -1168,7 +1172,7 @@ int plan_single(waa_batch* b, const PlanPass& pass, uint32_t id) {
     Node& p = b->nodes[b->edges[term.in_edges[0]].from];
     const uint32_t k = term.desc.kind;
     const bool identity = k == WAA_NODE_DESTINATION || k == WAA_NODE_ANALYSER ||
-                          (k == WAA_NODE_CONVOLVER && !term.has_ir) || (k == WAA_NODE_WAVESHAPER && !term.has_curve);
+                          (k == WAA_NODE_CONVOLVER && !term.has_ir) || (k == WAA_NODE_WAVESHAPER && !term.has_curve && !is_shaper_per_instance(term));
     // (not behind an output of a ChannelSplitterNode: a view has its owner's instance stride, the destination's layout is its own)
     if (identity && scc_of[id] < 0 && p.materialized && p.out_nch == term.in_nch && term.in_nch == term.out_nch && p.desc.kind != NODE_SPLITTER_PORT) {
       term.sig = p.sig;

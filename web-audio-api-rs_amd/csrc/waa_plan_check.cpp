@@ -69,6 +69,10 @@ static StepIo step_io_raw(const Step& st) {
       io.reads.push_back(st.comp.in.base);
       io.writes.push_back(st.comp.out.base);
       break;
+    case StepKind::ShaperInst:
+      io.reads.push_back(st.shaper.in.base);
+      io.writes.push_back(st.shaper.out.base);
+      break;
     case StepKind::ZeroFill:
       io.writes.push_back(st.zero_ptr);
       break;

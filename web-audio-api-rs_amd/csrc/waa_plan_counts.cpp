@@ -20,11 +20,12 @@ bool inputs_mix_in_order_differs(const waa_batch* b, const Node& n, uint64_t act
 namespace {
 
 // what the host knows about one instance: first and last active quantum of every source, the shortest and longest delay of
-// every DelayNode in quanta, the quanta in which a GainNode is zero; `sig` is all of it as bytes (instances with the same
-// signature are simulated once)
+// every DelayNode in quanta, the quanta in which a GainNode is zero, whether a WaveShaper's curve turns silence into a signal;
+// `sig` is all of it as bytes (instances with the same signature are simulated once)
 struct ReplayInputs {
   std::vector<double> lo, hi, shift, shift_hi;
   std::vector<std::vector<uint8_t>> zero_gain;
+  std::vector<uint8_t> wakes;  // WaveShaperNode: the centre of THIS instance's curve is not 0 (waveshaper.rs:498-509)
   std::string sig;
 };
 // per node and quantum: active or silent, channel count; of the node's output and of its mixed input
@@ -73,6 +74,7 @@ void replay_inputs(waa_batch* b, uint32_t inst, EndCache& end_cache, ReplayInput
   in.shift.assign(N, 0.);
   in.shift_hi.assign(N, 0.);
   in.zero_gain.assign(N, {});
+  in.wakes.assign(N, 0);
   in.sig.clear();
   auto add_sig = [&](double v) { in.sig.append(reinterpret_cast<const char*>(&v), sizeof v); };
   for (uint32_t id : b->order) {
@@ -142,6 +144,11 @@ void replay_inputs(waa_batch* b, uint32_t inst, EndCache& end_cache, ReplayInput
       if (!any) zero.clear();
       for (uint8_t z : zero) in.sig.push_back((char)z);
       in.sig.push_back('|');
+    } else if (kind == WAA_NODE_WAVESHAPER) {
+      const std::vector<float>* curve = n.curve_of(inst);
+      in.wakes[id] = curve && !(std::fabs(curve_at_zero(*curve)) < 1e-9f);
+      // (one curve per instance: two instances that differ only in this flag are two simulations)
+      if (n.per_inst_curve()) in.sig.push_back(in.wakes[id] ? 'w' : 's');
     }
   }
 }
@@ -209,9 +216,9 @@ void simulate(const waa_batch* b, const PlanPass& pass, const ReplayInputs& in, 
           c = (uint8_t)n.desc.i[0];  // channel_merger.rs:160-168: N channels when any input is active, else one silent channel
         } else if (kind == WAA_NODE_GAIN && !in.zero_gain[id].empty() && in.zero_gain[id][q]) {
           a = 0;
-        } else if (kind == WAA_NODE_WAVESHAPER && n.has_curve && !a) {
+        } else if (kind == WAA_NODE_WAVESHAPER && !a) {
           // a curve that does not map 0 to 0 turns silence into a signal (waveshaper.rs:498-509): active, mono
-          if (!(std::fabs(curve_at_zero(n)) < 1e-9f)) a = 1;
+          if (in.wakes[id]) a = 1;
         }
         if (a) {
           if (kind == WAA_NODE_STEREO_PANNER || kind == WAA_NODE_PANNER) c = 2;

@@ -69,7 +69,7 @@ void choose_folded_delays(waa_batch* b, const PlanPass& pass) {
       const Node& c = b->nodes[e.to];
       const uint32_t ck = c.desc.kind;
       const bool other_loop = scc_of[e.to] >= 0 && !(scc_of[e.to] == scc_of[id] && pass.block_loop(id));
-      if ((e.to_input & 0x80000000u) || other_loop || (ck == WAA_NODE_CONVOLVER && c.has_ir) || is_frozen_node(c) || is_compressor(c) || c.in_nch > 2 ||
+      if ((e.to_input & 0x80000000u) || other_loop || (ck == WAA_NODE_CONVOLVER && c.has_ir) || is_frozen_node(c) || is_compressor(c) || is_shaper_per_instance(c) || c.in_nch > 2 ||
           n.out_nch > 2 || is_routing_node(c))
         ok = false;
     }
@@ -95,6 +95,7 @@ void choose_materialisation(waa_batch* b, PlanPass& pass) {
     if (kind == WAA_NODE_DESTINATION || kind == WAA_NODE_ANALYSER || kind == WAA_NODE_CONVOLVER || kind == WAA_NODE_DELAY) mat = true;
     if (is_frozen_node(n)) mat = true;  // rendered node-major (waa_frozen.hip)
     if (is_compressor(n)) mat = true;   // rendered node-major (waa_compressor.hip)
+    if (is_shaper_per_instance(n)) mat = true;  // rendered node-major (waa_shaper_inst.hip)
     if (is_routing_node(n)) mat = true; // views / one route launch (waa_plan_route.cpp)
     // (a GainNode of a block-scheduled loop may ride on an input edge of its consumer, see choose_folded_delays)
     const bool relaxed = kind == WAA_NODE_GAIN && pass.block_loop(id);
@@ -105,7 +106,7 @@ void choose_materialisation(waa_batch* b, PlanPass& pass) {
       if (e.from == id && b->nodes[e.to].live) {
         live_consumers++;
         const Node& c = b->nodes[e.to];
-        if ((c.desc.kind == WAA_NODE_CONVOLVER && c.has_ir) || is_frozen_node(c) || is_compressor(c)) mat = true;
+        if ((c.desc.kind == WAA_NODE_CONVOLVER && c.has_ir) || is_frozen_node(c) || is_compressor(c) || is_shaper_per_instance(c)) mat = true;
         if (is_routing_node(c)) mat = true;  // the route launch and the port views read whole signals
         if (c.desc.kind == WAA_NODE_DELAY) {
           // a DelayNode mixes its inputs like a summing chain head (node_input_signal): materialised unless foldable
@@ -207,12 +208,12 @@ void choose_source_views(waa_batch* b, const PlanPass& pass) {
       const Node& c = b->nodes[e.to];
       const uint32_t ck = c.desc.kind;
       if ((e.to_input & 0x80000000u) || (scc_of[e.to] >= 0 && !pass.block_loop(e.to)) || (ck == WAA_NODE_CONVOLVER && c.has_ir) ||
-          is_frozen_node(c) || is_compressor(c) || ck == WAA_NODE_IIR_FILTER || is_routing_node(c))
+          is_frozen_node(c) || is_compressor(c) || is_shaper_per_instance(c) || ck == WAA_NODE_IIR_FILTER || is_routing_node(c))
         shared_ok = false;
     }
     if (!shared_ok && (n_live != 1 || consumer < 0)) continue;
     const Node& c = b->nodes[(uint32_t)(shared_ok ? 0 : consumer)];
-    const bool conv = !shared_ok && ((c.desc.kind == WAA_NODE_CONVOLVER && c.has_ir) || is_compressor(c));  // (both take a bounded view)
+    const bool conv = !shared_ok && ((c.desc.kind == WAA_NODE_CONVOLVER && c.has_ir) || is_compressor(c) || is_shaper_per_instance(c));  // (all take a bounded view)
     bool frozen_ok = shared_ok;
     if (!shared_ok && is_frozen_node(c) && pass.frozen_src[(uint32_t)consumer] == (int)id)
       // (a shaper that processes silent quanta would read them from the view: copy instead)

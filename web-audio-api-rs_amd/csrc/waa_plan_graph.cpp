@@ -238,7 +238,8 @@ void mark_live(waa_batch* b) {
 }
 
 // The node kinds that only static plans outside feedback loops render: refused inside a loop (in_loops), and anywhere in a
-// graph that needs the dynamic-count plan.
+// graph that needs the dynamic-count plan.  A WaveShaperNode with one curve per instance is one of them, and is refused with
+// oversample 2x / 4x wherever it stands.
 int refuse_static_only_nodes(waa_batch* b, const PlanPass& pass, bool in_loops) {
   const uint32_t N = (uint32_t)b->nodes.size();
   const char* where = in_loops ? "inside a feedback loop" : "in a graph that needs exact per-quantum channel counts (dyn_kernel)";
@@ -248,6 +249,19 @@ int refuse_static_only_nodes(waa_batch* b, const PlanPass& pass, bool in_loops) 
       return fail(WAA_ERR_OUT_OF_SCOPE, "DynamicsCompressorNode %u %s is out of scope: %s", i, where,
                   in_loops ? "its detector is rendered over the whole render by one launch, not quantum by quantum"
                            : "the node is rendered by static plans only");
+  for (uint32_t i = 0; i < N; i++) {
+    const Node& n = b->nodes[i];
+    if (!n.live || !is_shaper_per_instance(n)) continue;
+    // (wherever the node stands; asked once, by the first of the two calls)
+    if (in_loops && n.desc.i[0] != WAA_OVERSAMPLE_NONE)
+      return fail(WAA_ERR_OUT_OF_SCOPE, "WaveShaperNode %u with one curve per instance and oversample %s is out of scope: the oversampling transform stages "
+                                        "its one curve in LDS per workgroup; per-instance curves are rendered with oversample none only",
+                  i, n.desc.i[0] == WAA_OVERSAMPLE_X2 ? "2x" : "4x");
+    if (here(i))
+      return fail(WAA_ERR_OUT_OF_SCOPE, "WaveShaperNode %u with one curve per instance %s is out of scope: %s", i, where,
+                  in_loops ? "the node is rendered over the whole render by one launch, not quantum by quantum"
+                           : "per-instance curves are rendered by static plans only");
+  }
   for (uint32_t i = 0; i < N; i++) {
     const uint32_t k = b->nodes[i].desc.kind;
     if (here(i) && (k == WAA_NODE_CHANNEL_SPLITTER || k == WAA_NODE_CHANNEL_MERGER))

@@ -4,7 +4,7 @@
 //   waa_plan_counts.cpp  the replay of the reference's per-quantum silence and channel counts
 //   waa_plan_folds.cpp   frozen-node sources, folded delays, materialisation points, edge folds, source views, Biquad-into-Convolver
 //   waa_plan_dyn.cpp     dynamic-count groups;  waa_plan_loops.cpp  quantum-serial loops, delays;  waa_plan_sources.cpp, waa_plan_conv.cpp,
-//   waa_plan_comp.cpp, waa_plan_route.cpp, waa_plan_ops.cpp  the node kinds;  waa_plan_check.cpp  validation
+//   waa_plan_comp.cpp, waa_plan_shaper.cpp, waa_plan_route.cpp, waa_plan_ops.cpp  the node kinds;  waa_plan_check.cpp  validation
 #pragma once
 #include <vector>
 
@@ -44,7 +44,7 @@ struct PlanPass {
 void find_loops(const waa_batch* b, PlanPass& pass);                 // reads muted; writes scc_of, n_scc
 int collect_edges(waa_batch* b, const PlanPass& pass);              // reads muted, b->order; writes Node::in_edges / pin_edges / n_consumers, clears live / materialized
 void mark_live(waa_batch* b);                                        // reads the edges; writes Node::live
-int refuse_static_only_nodes(waa_batch* b, const PlanPass& pass, bool in_loops);  // live compressor / routing / per-instance-IR nodes
+int refuse_static_only_nodes(waa_batch* b, const PlanPass& pass, bool in_loops);  // live compressor / routing / per-instance-IR / per-instance-curve nodes
 int refuse_nested_source_modulation(const waa_batch* b);            // (prepass) reads Node::live
 int static_channel_counts(waa_batch* b, PlanPass& pass);            // writes Node::in_nch / out_nch, mixed_buffer_counts, b->force_dynamic
 void order_units(const waa_batch* b, PlanPass& pass);               // reads scc_of, the edges; writes units
@@ -112,6 +112,7 @@ int conv_block_size(const waa_batch* b, const Node& n);
 bool conv_fold_biquad_into_ir(const waa_batch* b, Node& conv, const Node& q);
 int plan_convolver(waa_batch* b, uint32_t id);
 int plan_compressor(waa_batch* b, uint32_t id);
+int plan_shaper_per_instance(waa_batch* b, uint32_t id);  // waa_plan_shaper.cpp
 // waa_plan_route.cpp: ChannelSplitterNode / ChannelMergerNode
 int desugar_output_ports(waa_batch* b);
 int plan_splitter(waa_batch* b, uint32_t id, bool producer_in_loop);

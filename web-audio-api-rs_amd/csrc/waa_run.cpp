@@ -86,6 +86,7 @@ static int run_step(waa_batch* b, const Step& st, uint32_t t0, uint32_t t1) {
       if (int e = launch_whole(b, st.slot_mac, st.comp, launch_compressor_detector)) return e;
       return launch_whole(b, st.slot_inv, st.comp, launch_compressor_apply);
     case StepKind::Route: return launch_whole(b, slot, st.route, launch_route);  // (never inside a feedback loop)
+    case StepKind::ShaperInst: return launch_whole(b, slot, st.shaper, launch_shaper_inst);  // (never inside a feedback loop: the whole render)
   }
   return fail(WAA_ERR_INVALID_STATE, "internal: step kind %d is not a StepKind", (int)st.kind);
 }
@@ -126,7 +127,8 @@ static int run_step_q(waa_batch* b, const Step& st, uint32_t q0, uint32_t q1) {
     case StepKind::BiquadTileDigest:
     case StepKind::BiquadLanes:
     case StepKind::Compressor:
-    case StepKind::Route: break;
+    case StepKind::Route:
+    case StepKind::ShaperInst: break;
   }
   return fail(WAA_ERR_INVALID_STATE, "internal: step kind %d inside a quantum-blocked loop", (int)st.kind);
 }

@@ -7,8 +7,8 @@ step for the Python mirror (round-5 review, missing 4): contexts built one by on
 (`OfflineAudioContext(channels, length, rate)` with n_instances = 1), are bucketed by `shape_key` — the graph (node kinds, options,
 channel configuration, connections), the context's format, the SHAPES of per-context payloads (an AudioBufferSource's channel count,
 length and rate, and on the device library the padded length of an IIRFilterNode's coefficients, which become per-instance sets of the
-batch) and the identity of payloads a batch shares (a convolver's impulse response, a shaper's curve, and on other bindings
-IIR coefficients and an oscillator's PeriodicWave, which the device library takes per instance) — every bucket is merged into one
+batch) and the identity of payloads a batch shares (a convolver's impulse response, an oversampled shaper's curve, and on other bindings
+IIR coefficients, an oscillator's PeriodicWave and a plain shaper's curve, which the device library takes per instance) — every bucket is merged into one
 batch (per-context AudioBuffers, AudioParam values and automation, start / stop / loop settings become per-instance settings of the batch), rendered, and the AudioBuffers are handed back in the callers' order.
 Contexts with suspend callbacks render on their own (their callbacks may do anything)."""
 from __future__ import annotations
@@ -37,6 +37,11 @@ def _osc_wave(nd):
     return nd._inst_waves.get(0, nd.periodic_wave)
 
 
+def _curve(nd):
+    """the curve context 0 of a WaveShaperNode renders with (None: it passes its input through)"""
+    return nd._inst_curves.get(0, nd.curve)
+
+
 def _wave_id(w) -> tuple:
     return ("table", _digest(w.table)) if w.table is not None else (_digest(w.real), _digest(w.imag), w.disable_normalization)
 
@@ -50,8 +55,13 @@ def _node_key(nd) -> tuple:
         pcm = getattr(nd, "_pcm", None)
         key.append(None if pcm is None else (_digest(pcm[0]), pcm[1]))
     if isinstance(nd, WaveShaperNode):
-        curve = getattr(nd, "curve", None)
-        key.append(None if curve is None else _digest(curve))
+        curve = _curve(nd)
+        if curve is not None and nd.context._b.prefix == "waa_" and nd.oversample == "none":
+            # the device library takes one curve per context: contexts that differ only in their curves share a batch (every curve
+            # keeps its own length); an oversampled shaper stages its one curve per workgroup and keeps the digest
+            key.append("curve")
+        else:
+            key.append(None if curve is None else _digest(curve))
     if isinstance(nd, IIRFilterNode):
         ff, fb = _iir_set(nd)  # (a single context's own set: its instance-0 set if it was given one, else the constructor's)
         if nd.context._b.prefix == "waa_":
@@ -137,6 +147,15 @@ def _merge(bucket: Sequence[OfflineAudioContext]) -> OfflineAudioContext:
             if not all(np.array_equal(ff, sets[0][0]) and np.array_equal(fb, sets[0][1]) for ff, fb in sets[1:]):
                 for i, (ff, fb) in enumerate(sets[1:], start=1):
                     cn.set_coefficients(ff, fb, instance=i)
+        if isinstance(cn, WaveShaperNode) and _curve(cn) is not None:
+            # every context's effective curve (_curve) becomes its instance's; equal curves everywhere: the node stays shared
+            curves = [_curve(nd) for nd in [cn] + others]
+            cn._inst_curves = {}
+            cn.curve = curves[0]
+            if not all(np.array_equal(c, curves[0]) for c in curves[1:]):
+                cn.curve = None
+                for i, c in enumerate(curves):
+                    cn.set_curve(c, instance=i)
         if isinstance(cn, OscillatorNode) and _osc_wave(cn) is not None:
             # every context's effective wave (_osc_wave) becomes its instance's; equal waves everywhere: the node stays shared
             waves = [_osc_wave(nd) for nd in [cn] + others]

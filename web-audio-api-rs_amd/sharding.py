@@ -108,7 +108,7 @@ def render_sharded(build: Callable, host_in, host_out, devices: Sequence[int] = 
         `device`; `src` is the AudioBufferSourceNode that receives the contexts' buffers.  Called once for the graph's shape
         and once per sub-batch (on the library's thread) to configure that sub-batch: node payloads, params, schedules.
     pass_first: build is called as build(n_instances, device, first=k) with the index of the sub-batch's first context (0 for the
-        shape), for payloads that differ from context to context (per-instance impulse responses, per-instance IIR coefficients):
+        shape), for payloads that differ from context to context (per-instance impulse responses, per-instance IIR coefficients, per-instance WaveShaper curves):
         it configures contexts [k, k + n_instances).  Leave `reuse` off then.
     host_in:  [N, channels, frames] float32 — or, with pcm16=True, [N, frames, channels] int16 (decoded WAV data: half
         the upload, converted on the device) — C-contiguous numpy array or pinned torch tensor.
