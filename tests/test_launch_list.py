@@ -500,6 +500,272 @@ BRANCHES = {
 }
 
 
+# ---- the item tables of the dynamic-count plan (dyn_items.txt): one small graph per line of waa_plan_dyn.cpp that the graphs above
+# ---- do not execute (measured with gcov on the planner as it was before plan_dynamic_groups was split)
+def _burst(c, n_ch=2, frames=RQ * 20, start=0.0, seed0=5):
+    """a source that ends long before the render does: the count of its signal changes mid-render"""
+    s = c.create_buffer_source()
+    s.set_buffer_batch(white_noise(c.n_instances, n_ch, frames, seed0=seed0) * np.float32(0.5), SR)
+    s.start_at(start)
+    return s
+
+
+def _mono_and_burst(c, n_ch=2, seed0=30):
+    """a mono source that plays throughout and a wider one that joins late and ends early, to be summed by a count-sensitive node"""
+    return _source(c, n_ch=1, seed0=seed0, scale=0.5), _burst(c, n_ch, RQ * 30, RQ * 12 / SR, seed0 + 1)
+
+
+def _gain_modulated_from_its_loop(be, n_mod=1, outside=False):
+    """tests/test_cycles.py: src -> Delay -> Gain(g) -> back, Delay -> Gain(depth) -> g.gain, n_mod times; outside: an LFO on g.gain
+    too, made first so that the param sums it last"""
+    c = _ctx(be)
+    lfo = c.create_oscillator(type_="sine", frequency=7.0) if outside else None
+    s = _source(c)
+    d = c.create_delay(1.0, delay_time=0.01)
+    g = c.create_gain(gain=0.3)
+    s.connect(d)
+    d.connect(g).connect(d)
+    for _ in range(n_mod):
+        d.connect(c.create_gain(gain=0.2)).connect(g.gain)
+    if outside:
+        lfo.connect(g.gain)
+        lfo.start()
+    d.connect(c.destination())
+    return c
+
+
+def g_dyn_gain_modulated_from_its_loop(be):
+    return _gain_modulated_from_its_loop(be)
+
+
+def g_dyn_gain_param_with_five_loop_inputs_refused(be):
+    return _gain_modulated_from_its_loop(be, n_mod=5)
+
+
+def g_dyn_gain_param_from_inside_and_outside_refused(be):
+    return _gain_modulated_from_its_loop(be, outside=True)
+
+
+def g_dyn_filter_param_from_its_loop_refused(be):   # tests/test_cycles.py
+    c = _ctx(be)
+    s = _source(c)
+    d = c.create_delay(1.0, delay_time=0.01)
+    bq = c.create_biquad_filter(type_="lowpass", frequency=800.0)
+    s.connect(d)
+    d.connect(bq).connect(c.create_gain(gain=0.3)).connect(d)
+    d.connect(c.create_gain(gain=200.0)).connect(bq.frequency)
+    d.connect(c.destination())
+    return c
+
+
+def _conv_behind_a_group(be, ir):
+    """tests/test_dynamic_counts.py: stereo burst, silence, a mono source, a second stereo burst into a convolver"""
+    c = _ctx(be)
+    conv = c.create_convolver(buffer=waa.AudioBuffer(ir, SR))
+    for s in (_burst(c, 2, RQ * 6, RQ * 2 / SR, 61), _burst(c, 1, RQ * 10, RQ * 20 / SR, 62), _burst(c, 2, RQ * 8, RQ * 26 / SR, 63)):
+        s.connect(conv)
+    conv.connect(c.destination())
+    return c
+
+
+def g_dyn_conv_mono_response_stereo_input(be):   # channel 1 in compacted time
+    return _conv_behind_a_group(be, _decaying_ir(1, 1700, 64))
+
+
+def g_dyn_conv_response_with_zero_segments(be):  # exact zeros inside the response and below 1e-6 at its end: the noise floor's segment masks
+    ir = _decaying_ir(2, 4000, 65)
+    ir[0, 1024:2048] = 0.0
+    ir[1, 2048:3072] = 0.0
+    ir[:, 3500:] = 0.0
+    return _conv_behind_a_group(be, ir)
+
+
+def g_dyn_analyser(be):
+    c = _ctx(be)
+    pan, an = c.create_stereo_panner(pan=0.3), c.create_analyser()
+    for s in _mono_and_burst(c):
+        s.connect(pan)
+    pan.connect(an).connect(c.destination())
+    return c
+
+
+def g_dyn_shaper_without_a_curve(be):
+    c = _ctx(be)
+    sh = c.create_wave_shaper()
+    for s in _mono_and_burst(c):
+        s.connect(sh)
+    sh.connect(c.create_stereo_panner(pan=0.25)).connect(c.destination())
+    return c
+
+
+def g_dyn_hrtf_behind_its_group(be):
+    c = _ctx(be)
+    pn = c.create_panner(panning_model="HRTF", position=(0.8, 0.3, -0.6))
+    g = c.create_gain(gain=0.8)
+    _burst(c).connect(g)
+    _burst(c, 1, RQ * 30, RQ * 5 / SR, 6).connect(g)
+    g.connect(pn).connect(c.destination())
+    return c
+
+
+def g_dyn_equal_power_panner(be):   # both laws of the PannerNode
+    c = _ctx(be)
+    pn = c.create_panner(distance_model="inverse", ref_distance=1.0, position=(1.5, 0.0, -1.0))
+    for s in _mono_and_burst(c):
+        s.connect(pn)
+    pn.connect(c.destination())
+    return c
+
+
+def g_qloop_many_modulators_refused(be):   # the modulators' sum takes a launch that is not a param's own
+    c = _ctx(be, frames=RQ * 70 + 33)
+    d = c.create_delay(0.1, delay_time=0.01)
+    sh = c.create_wave_shaper(curve=CURVE, oversample="2x")
+    g = c.create_gain(gain=0.45)
+    for k in range(10):
+        lfo = c.create_oscillator(type_="sine", frequency=3.0 + k)
+        lfo.connect(g.gain)
+        lfo.start()
+    _burst(c).connect(d)
+    d.connect(sh).connect(g).connect(d)
+    sh.connect(c.destination())
+    return c
+
+
+def g_dyn_oscillator_source(be):
+    c = _ctx(be)
+    osc = c.create_oscillator(type_="sawtooth", frequency=330.0)
+    osc.start_at(RQ * 2.25 / SR)
+    pan = c.create_stereo_panner(pan=-0.4)
+    osc.connect(pan)
+    _burst(c, start=RQ * 20 / SR).connect(pan)
+    pan.connect(c.destination())
+    return c
+
+
+def g_dyn_param_driven_by_a_pending_member(be):  # the filter's group is launched first, then the param's summing chain, then the gain's
+    c = _ctx(be)
+    bq = c.create_biquad_filter(type_="lowpass", frequency=800.0)
+    g = c.create_gain(gain=0.3)
+    for s in _mono_and_burst(c):
+        s.connect(bq)
+    bq.connect(c.destination())
+    bq.connect(g.gain)
+    _burst(c, 1, RQ * 30, seed0=6).connect(g).connect(c.destination())
+    return c
+
+
+def g_qloop_pair_inside_one_segment(be):   # tests/test_frozen_loops.py: the breaking delay sits behind the node, writer and reader in one launch
+    c = _ctx(be, frames=RQ * 70 + 33)
+    mix = c.create_gain(gain=1.0)
+    sh = c.create_wave_shaper(curve=CURVE, oversample="4x")
+    d = c.create_delay(0.1, delay_time=0.02)
+    _burst(c, 2, RQ * 25, seed0=12).connect(mix)
+    mix.connect(sh).connect(c.create_gain(gain=0.5)).connect(d).connect(mix)
+    sh.connect(c.destination())
+    return c
+
+
+def g_qloop_two_split_pairs(be):           # 480 and 960 frames across the cut: the shorter delay bounds the block (3 quanta)
+    c = _ctx(be, frames=RQ * 70 + 33)
+    s = _burst(c)
+    sh = c.create_wave_shaper(curve=CURVE, oversample="2x")
+    g = c.create_gain(gain=0.3)
+    for t in (0.02, 0.01):
+        d = c.create_delay(0.1, delay_time=t)
+        s.connect(d)
+        d.connect(sh)
+        g.connect(d)
+    sh.connect(g)
+    sh.connect(c.destination())
+    return c
+
+
+def g_qloop_conv_mono_response_refused(be):
+    c = _ctx(be, frames=RQ * 70 + 33)
+    d = c.create_delay(0.1, delay_time=0.005)
+    cv = c.create_convolver(buffer=waa.AudioBuffer(_decaying_ir(1, 300, 7), SR))
+    _burst(c).connect(d)
+    d.connect(cv).connect(c.create_gain(gain=0.25)).connect(d)
+    cv.connect(c.destination())
+    return c
+
+
+def g_dyn_pipeline_with_a_loop_and_a_pair(be):   # a delay pair in front of a short loop around an IIR filter: neither is cut
+    c = _ctx(be)
+    d0 = c.create_delay(0.05, delay_time=0.002)
+    d = c.create_delay(0.05, delay_time=0.003)
+    f = c.create_iir_filter([0.2, 0.3, 0.1], [1.0, -0.5, 0.2])
+    _burst(c).connect(c.create_biquad_filter(type_="lowpass", frequency=900.0)).connect(d0).connect(d)
+    d.connect(f).connect(c.create_gain(gain=0.5)).connect(d)
+    f.connect(c.create_stereo_panner(pan=0.2)).connect(c.create_biquad_filter(type_="highpass", frequency=200.0)).connect(c.destination())
+    return c
+
+
+def g_dyn_wide_source_into_a_convolver(be):   # (the convolver's channel config keeps its input stereo)
+    c = _ctx(be, n_out=4)
+    cv = c.create_convolver(buffer=waa.AudioBuffer(_decaying_ir(4, 300, 7), SR))
+    _burst(c, 4).connect(cv).connect(c.destination())
+    return c
+
+
+def g_dyn_nine_inputs_refused(be):
+    c = _ctx(be)
+    pan = c.create_stereo_panner(pan=0.1)
+    for k in range(9):
+        _burst(c, 1 + k % 2, RQ * (10 + k), RQ * k / SR, 20 + k).connect(pan)
+    pan.connect(c.destination())
+    return c
+
+
+def _filter_chain(be, n_ch, n_filters):
+    c = _ctx(be, n_out=n_ch)
+    head = c.create_biquad_filter(type_="lowpass", frequency=5000.0)
+    for s in _mono_and_burst(c, n_ch):
+        s.connect(head)
+    for _ in range(n_filters - 1):
+        head = head.connect(c.create_biquad_filter(type_="lowpass", frequency=5000.0))
+    head.connect(c.destination())
+    return c
+
+
+def g_dyn_49_members_refused(be):
+    return _filter_chain(be, 2, 48)
+
+
+def g_dyn_local_memory_refused(be):  # 5.1 signals: 40 items do not fit 160 KB
+    return _filter_chain(be, 6, 39)
+
+
+# the graphs above that plan a dynamic-count group, and those made for the lines they leave out
+DYN_ITEMS = {name: NAMED[name] for name in ("qloop_shaper_2x", "qloop_hrtf", "qloop_automated", "qloop_conv_and_shaper")}
+DYN_ITEMS.update({name: BRANCHES[name][:2] for name in ("frozen_fan_in", "mono_shaper_into_a_wide_downmix", "bus_grows_input_by_input",
+                                                        "mixed_buffer_widths", "short_loop_around_an_iir")})
+DYN_ITEMS.update({
+    "gain_modulated_from_its_loop": (g_dyn_gain_modulated_from_its_loop, {}),
+    "conv_mono_response_stereo_input": (g_dyn_conv_mono_response_stereo_input, {}),
+    "conv_response_with_zero_segments": (g_dyn_conv_response_with_zero_segments, {}),
+    "conv_without_the_noise_floor": (g_dyn_conv_response_with_zero_segments, {"WAA_NO_CONV_NOISE_FLOOR": "1"}),
+    "analyser": (g_dyn_analyser, {}), "shaper_without_a_curve": (g_dyn_shaper_without_a_curve, {}),
+    "hrtf_behind_its_group": (g_dyn_hrtf_behind_its_group, {}), "oscillator_source": (g_dyn_oscillator_source, {}),
+    "equal_power_panner": (g_dyn_equal_power_panner, {}),
+    "param_driven_by_a_pending_member": (g_dyn_param_driven_by_a_pending_member, {}),
+    "qloop_pair_inside_one_segment": (g_qloop_pair_inside_one_segment, {}), "qloop_two_split_pairs": (g_qloop_two_split_pairs, {}),
+    "qloop_one_quantum": (g_qloop_two_split_pairs, {"WAA_LOOP_ONE_QUANTUM": "1"}),
+    "short_loop_around_an_iir_one_stage": (g_short_loop_around_an_iir, {"WAA_DYN_STAGES": "1"}),
+    "pipeline_with_a_loop_and_a_pair": (g_dyn_pipeline_with_a_loop_and_a_pair, {}),
+    "wide_source_into_a_convolver": (g_dyn_wide_source_into_a_convolver, {}), "nine_inputs_refused": (g_dyn_nine_inputs_refused, {}),
+    "49_members_refused": (g_dyn_49_members_refused, {}), "local_memory_refused": (g_dyn_local_memory_refused, {}),
+    "filter_param_from_its_loop_refused": (g_dyn_filter_param_from_its_loop_refused, {}),
+    "gain_param_with_five_loop_inputs_refused": (g_dyn_gain_param_with_five_loop_inputs_refused, {}),
+    "gain_param_from_inside_and_outside_refused": (g_dyn_gain_param_from_inside_and_outside_refused, {}),
+    "qloop_conv_mono_response_refused": (g_qloop_conv_mono_response_refused, {}),
+    "qloop_frozen_node_refused": (g_qloop_hrtf, {"WAA_NO_FROZEN_LOOPS": "1"}),
+    "qloop_matrix_shaper_refused": (g_qloop_shaper_2x, {"WAA_OS_MATRIX": "1"}),
+    "qloop_many_modulators_refused": (g_qloop_many_modulators_refused, {}),
+})
+
+
 def random_graph(seed, frozen):
     def build(be):
         c, _ = build_random_graph(be, seed, frozen=frozen)
@@ -591,6 +857,27 @@ def test_branch_launch_lists_are_what_they_were(hip, monkeypatch):
         assert phrase in got, (name, got)
         assert got == want[name], name
         assert "\nlaunch 0: " in got or (name.endswith("_refused") and got.startswith("refused with status 4:")), got
+
+
+def dyn_items_text(be, setenv, delenv):
+    """dyn_items.txt: like named.txt, for DYN_ITEMS, with the item tables (WAA_PLAN_DYN_ITEMS=1) behind every text"""
+    return "".join(f"==== {name}\n{describe(be, build, dict(switches, WAA_PLAN_DYN_ITEMS='1'), setenv, delenv)}"
+                   for name, (build, switches) in DYN_ITEMS.items())
+
+
+def test_dynamic_item_tables_are_what_they_were(hip, monkeypatch):
+    """what the dynamic-count planner writes into the DynItem tables, the DynDescs and the ConvCodeDescs — which the launch list
+    does not show — and its refusals with status and text: written by plan_dynamic_groups as it was while it was one function of
+    700 lines, with the same dump patched in"""
+    want = _sections(_golden("dyn_items"))
+    assert list(want) == list(DYN_ITEMS)
+    for name, (build, switches) in DYN_ITEMS.items():
+        got = describe(hip, build, dict(switches, WAA_PLAN_DYN_ITEMS="1"), monkeypatch.setenv, monkeypatch.delenv)
+        assert got == want[name], name
+        if name.endswith("_refused"):
+            assert got.startswith("refused with status 4:"), got
+        else:
+            assert re.search(r"^launch \d+ dyn: n_items=\d+ ", got, re.M) and re.search(r"^launch \d+ item 0: kind=", got, re.M), got
 
 
 def test_random_launch_lists_are_what_they_were(hip, monkeypatch):

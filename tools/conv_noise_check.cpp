@@ -7,7 +7,7 @@
 #include "../web-audio-api-rs_amd/csrc/waa_conv_noise.hpp"
 
 extern "C" {
-// the planner's part (waa_plan_dyn.cpp::plan_dyn_convolver): segments of the trimmed response and which of them hold a tap
+// the planner's part (waa_plan_dyn.cpp::conv_noise_segments): segments of the trimmed response and which of them hold a tap
 void cn_describe(const float* h, uint64_t len, uint32_t* seg_count, uint64_t* seg_mask) {
   uint64_t l = len;
   while (l > 0 && std::fabs(h[l - 1]) < 0.000001f) l--;

@@ -18,6 +18,60 @@ int fail(int code, const char* fmt, ...) {
   va_end(ap);
   return code;
 }
+// WAA_PLAN_DYN_ITEMS=1 (measurement build): what the dynamic-count planner puts into the item tables of its dyn_kernel launches
+// and into the code kernels' descriptors, without an address in it (tests/test_launch_list.py: dyn_items.txt).  Plan-only batches
+// only: their tables are host memory.
+static void describe_dyn_items(const waa_batch* b, std::string& text) {
+  char l[640];
+  auto set = [](const void* p) { return p ? 1 : 0; };
+  auto param = [&](const char* name, const ParamRef& p) {
+    std::string s = std::string(" ") + name + "=m" + std::to_string(p.mode);
+    if (p.mode == 0 && p.base)
+      for (uint32_t i = 0; i < std::min(b->n_inst, 4u); i++) {
+        snprintf(l, sizeof l, "%c%.9g", i ? ',' : ':', (double)p.base[i]);
+        s += l;
+      }
+    return s;
+  };
+  for (size_t k = 0; k < b->steps.size(); k++) {
+    const Step& st = b->steps[k];
+    if (st.kind == StepKind::ConvCodes) {
+      const ConvCodeDesc& c = st.ccode;
+      snprintf(l, sizeof l, "launch %zu conv_codes: cout=%d ir_nch=%d impulse_length=%llu noise=%d in_test_nch=%d state=%d nir=", k, c.cout, c.ir_nch,
+               (unsigned long long)c.impulse_length, c.noise, c.in_test_nch, set(c.state));
+      text += l;
+      for (int j = 0; j < 4; j++) {
+        snprintf(l, sizeof l, "%s%u:%llx", j ? "," : "", c.nir[j].seg_count, (unsigned long long)c.nir[j].seg_mask);
+        text += l;
+      }
+      text += "\n";
+    }
+    if (st.kind != StepKind::Dyn) continue;
+    const DynDesc& d = st.dyn;
+    snprintf(l, sizeof l, "launch %zu dyn: n_items=%d cmax=%d n_stages=%d stage_begin=", k, d.n_items, d.cmax, d.n_stages);
+    text += l;
+    for (int s = 0; s <= d.n_stages; s++) text += (s ? "," : "") + std::to_string(d.stage_begin[s]);
+    snprintf(l, sizeof l, " split_ok=%u save_f=%d save_i=%d\n", d.split_ok, set(d.save_f), set(d.save_i));
+    text += l;
+    for (int i = 0; i < d.n_items; i++) {
+      const DynItem& it = d.items[i];
+      snprintf(l, sizeof l, "launch %zu item %d: kind=%d dk=%d cc=%d mode=%d interp=%d n_in=%d nch_pub=%d publish_upmix=%d compact_ch1=%d flags=%d writer_item=%d in_cycle=%d num_quanta=%d in=[",
+               k, i, it.kind, it.dk, it.cc, it.mode, it.interp, it.n_in, it.nch_pub, it.publish_upmix, it.compact_ch1, it.flags, it.writer_item,
+               it.in_cycle, it.num_quanta);
+      text += l;
+      for (int j = 0; j < it.n_in; j++) {
+        snprintf(l, sizeof l, "%s%d/%d/code%d/remap%d", j ? " " : "", it.in[j].item, it.in[j].nch, set(it.in[j].code), set(it.in[j].remap));
+        text += l;
+      }
+      text += "] op.kind=" + std::to_string(it.op.kind) + param("p0", it.op.p0) + param("p1", it.op.p1) + param("p2", it.op.p2) + param("alt1", it.alt1) +
+              param("alt2", it.alt2);
+      snprintf(l, sizeof l, " pmod_n=%d pmod_item=%d,%d,%d,%d pmod_min=%.9g pmod_max=%.9g pmod_def=%.9g out=%d out_code=%d aux32=%d xline=%d xaux32=%d xstate=%d\n",
+               it.pmod_n, it.pmod_item[0], it.pmod_item[1], it.pmod_item[2], it.pmod_item[3], (double)it.pmod_min, (double)it.pmod_max, (double)it.pmod_def,
+               set(it.out.base), set(it.out_code), set(it.aux32), set(it.xline.base), set(it.xaux32), set(it.xstate));
+      text += l;
+    }
+  }
+}
 }  // namespace host
 }  // namespace waa
 
@@ -346,6 +400,7 @@ waa_status waa_plan_describe(waa_batch* b, char* buf, size_t cap, size_t* needed
     for (uint32_t q : b->qgroup_quanta) text += " " + std::to_string(q);
     text += "\n";
   }
+  if (b->dry && measure_switch("WAA_PLAN_DYN_ITEMS")) describe_dyn_items(b, text);
   if (needed) *needed = text.size();
   if (buf && cap) {
     const size_t n = std::min(cap - 1, text.size());

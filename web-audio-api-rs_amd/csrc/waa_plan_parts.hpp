@@ -3,9 +3,12 @@
 //   waa_plan_graph.cpp   processing order, feedback loops, edges in summing order, liveness, static channel counts, units
 //   waa_plan_counts.cpp  the replay of the reference's per-quantum silence and channel counts
 //   waa_plan_folds.cpp   frozen-node sources, folded delays, materialisation points, edge folds, source views, Biquad-into-Convolver
-//   waa_plan_dyn.cpp     dynamic-count groups;  waa_plan_loops.cpp  quantum-serial loops, delays;  waa_plan_sources.cpp, waa_plan_conv.cpp,
+//   waa_plan_dyn.cpp     dynamic-count groups;  waa_plan_dyn_loop.cpp  ... their loops with node-major members inside
+//   waa_plan_loops.cpp   quantum-serial loops, delays;  waa_plan_sources.cpp, waa_plan_conv.cpp,
 //   waa_plan_comp.cpp, waa_plan_shaper.cpp, waa_plan_route.cpp, waa_plan_ops.cpp  the node kinds;  waa_plan_check.cpp  validation
 #pragma once
+#include <map>
+#include <set>
 #include <vector>
 
 #include "waa_host.hpp"
@@ -63,6 +66,30 @@ int alloc_signal(waa_batch* b, Node& n);
 int plan_single(waa_batch* b, const PlanPass& pass, uint32_t id);   // one node outside a loop or of a block-scheduled loop, with the chain that ends in it
 // waa_plan_dyn.cpp
 int plan_dynamic_groups(waa_batch* b, const PlanPass& pass);
+// ... and what its parts share (waa_plan_dyn.cpp, waa_plan_dyn_loop.cpp)
+// A DelayNode of a quantum-blocked loop whose writer and reader fall into different segments talks through memory (DynItem::xline ...)
+struct XDelay {
+  SignalRef line{};
+  uint32_t* aux32 = nullptr;
+  int32_t* state = nullptr;
+  int writer_seg = -1, reader_seg = -1;
+};
+struct DynPlan {
+  waa_batch* b;
+  const PlanPass& pass;
+  uint64_t cs;                         // b->code_stride
+  std::map<uint32_t, size_t> vpos;     // position of every vertex in the processing order
+  std::vector<uint32_t> pending;       // vertices of the current group
+  std::set<uint32_t> pending_nodes;    // their node ids
+  std::vector<uint8_t> planned_node;
+  int cur_qgroup = -1;                 // the quantum-blocked loop whose segments are being planned, or -1
+  std::map<uint32_t, XDelay> xdelay;   // ... its delay node id -> cross-segment resources (only pairs that ARE split)
+};
+bool is_node_major(const Node& n);  // rendered node-major behind the group that publishes its mixed input (convolver with a response, frozen-state node): a loop is cut there
+int enqueue_vertex(DynPlan& p, uint32_t v);
+int flush_group(DynPlan& p);                     // one dyn_kernel launch for the pending vertices
+int plan_dyn_convolver(DynPlan& p, uint32_t id);  // FFT steps + the code kernel behind the group that published the convolver's mixed input
+int plan_quantum_blocked_loop(DynPlan& p, const std::vector<uint32_t>& verts);  // waa_plan_dyn_loop.cpp
 // vertices of the expanded graph the cycle breaker works on: a DelayNode is two (writer `id`, reader `id | VTX_READER`)
 constexpr uint32_t VTX_READER = 0x80000000u;
 

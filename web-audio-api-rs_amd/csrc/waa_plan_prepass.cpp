@@ -338,7 +338,7 @@ int plan_batch(waa_batch* b) {
   return e;
 }
 
-// Quantum-blocked loops rendered in blocks of several quanta are optimistic about ONE thing (waa_plan_dyn.cpp: the ring's channel
+// Quantum-blocked loops rendered in blocks of several quanta are optimistic about ONE thing (waa_plan_dyn_loop.cpp: the ring's channel
 // count as the reader of a split delay pair sees it).  Every entry point that hands out results waits for the render and looks at
 // the writers' flags first; a flagged render is repeated with one quantum per block — the round-5 form, always right.
 int settle_loops(waa_batch* b) {
