@@ -79,6 +79,27 @@ waa_status waa_oscillator_get_wavetable(waa_batch* batch, uint32_t node, uint32_
  * waa_batch_rearm keeps the curves, like everything but the audio. */
 waa_status waa_waveshaper_set_curve_instance(waa_batch* batch, uint32_t node, uint32_t instance, const float* curve, uint32_t n);
 
+/* BiquadFilterNode::set_type of ONE context of the batch (src/node/biquad_filter.rs:28-373 for what a type computes, the type
+ * message at :901-906): in the reference every context builds its own BiquadFilterNode with its own type.  Replaces one batch,
+ * one plan and one launch sequence per filter type (up to eight): a random-equaliser augmentation where every clip goes through
+ * its own lowpass / peaking / shelf with its own frequency, Q and gain, a sweep over filter designs, serving requests that
+ * differ in their filter type.  The node's four AudioParams were per instance already.
+ *
+ * type: 0 .. 7 as in waa_node_desc.i[0] of a BIQUAD node; anything else is "bad biquad type" (WAA_ERR_INVALID_ARGUMENT), the
+ * refusal of waa_batch_create.  Refused once the batch is planned (InvalidStateError), for an instance >= n_instances and for a
+ * node of another kind (WAA_ERR_INVALID_ARGUMENT).  instance = WAA_ALL_INSTANCES sets the node's shared type (i[0]) and leaves
+ * the types given to single instances alone; an instance without a type of its own uses the shared one.  As set_type in the
+ * reference, the call may be repeated: a later call for the same instance replaces the earlier one.
+ *
+ * A node whose instances all end up with the same type plans and renders exactly as a shared node of that type.  Where the types
+ * differ, constant and k-rate coefficient rows are built per instance from the instance's type (they were per instance already);
+ * an a-rate node gets one table row per instance even under one shared automation (40 B per frame and instance, DESIGN.md 3.1
+ * "Per-context types"), written by biquad_coef_inst_kernel with the arithmetic of the shared kernel; and a Biquad in front of a
+ * ConvolverNode is not folded into the impulse response — the exact-order filter stage renders it.  Called at a suspend point it
+ * applies to the whole render, like the shared option.  waa_batch_rearm keeps the types, like everything
+ * but the audio. */
+waa_status waa_biquad_set_type_instance(waa_batch* batch, uint32_t node, uint32_t instance, int32_t type);
+
 #ifdef __cplusplus
 }
 #endif

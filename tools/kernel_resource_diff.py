@@ -31,6 +31,7 @@ for f in files:
         if ro[k]!=rn[k]: print(b, k[:90], 'old',ro[k],'new',rn[k]); changed+=1
         else: same+=1
     only_new+=[(b,k) for k in sorted(set(rn)-set(ro))]
+    for k in sorted(set(rn)-set(ro)): print(b, k[:90], 'new kernel', rn[k])
 for f in sorted(os.listdir(ROOT+'/web-audio-api-rs_amd/csrc')):
     if f.endswith('.hip') and 'web-audio-api-rs_amd/csrc/'+f not in files:
         rn=res(ROOT+'/web-audio-api-rs_amd/csrc/'+f, ROOT+'/web-audio-api-rs_amd/csrc')

@@ -207,6 +207,7 @@ ABI_DEVICE = {
     "oscillator_set_wavetable_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, C.c_uint32]),
     "oscillator_get_wavetable": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, C.c_uint32]),
     "waveshaper_set_curve_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, C.c_uint32]),
+    "biquad_set_type_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, C.c_int32]),
 }
 
 
@@ -779,26 +780,85 @@ class BiquadFilterNode(AudioNode):
     def __init__(self, ctx, type_="lowpass", frequency=350.0, detune=0.0, q=1.0, gain=0.0, **kw):
         super().__init__(ctx, **kw)
         self.type_ = type_
+        self._inst_types = {}  # instance -> type name: one type per context (waa_biquad_set_type_instance)
         self.frequency = AudioParam(self, 0, frequency)
         self.detune = AudioParam(self, 1, detune)
         self.q = AudioParam(self, 2, q)
         self.gain = AudioParam(self, 3, gain)
         self.params = [self.frequency, self.detune, self.q, self.gain]
 
-    def set_type(self, type_: str):
-        self.type_ = type_
+    def set_type(self, type_: str, instance: int = ALL):
+        """instance = ALL: the type of every context without one of its own.  instance = i: context i's own type (every context of
+        the reference sets the type of its own node, biquad_filter.rs:901-906).  May be called any number of times; the last call
+        for an instance wins.  The two forms differ in their refusals: the per-instance form refuses an unknown name ("bad biquad
+        type"), an instance out of range and a call after the batch exists (InvalidStateError) at once; the ALL form is as it was
+        before instances had types — the name is looked up when the batch is created (an unknown one is a KeyError there), and a
+        call after that is not refused and is not sent to the batch that exists."""
+        if instance == ALL:
+            self.type_ = type_
+            return self
+        if type_ not in BIQUAD_TYPE:
+            raise WaaError(1, "bad biquad type")
+        if self.context._handle is not None:
+            raise WaaError(3, "InvalidStateError - the batch is frozen once rendering has started")
+        if not 0 <= int(instance) < self.context.n_instances:
+            raise WaaError(1, f"instance {instance} out of range")
+        self._inst_types[int(instance)] = type_
         return self
+
+    def set_type_batch(self, types):
+        """types: a sequence of n_instances type names, one per context"""
+        n = self.context.n_instances
+        if len(types) != n:
+            raise WaaError(1, f"set_type_batch takes n_instances = {n} types, got {len(types)}")
+        for i, t in enumerate(types):
+            self.set_type(t, instance=i)
+        return self
+
+    def type_of(self, instance: int) -> str:
+        """the type context `instance` renders with: its own, or the shared one"""
+        if not 0 <= int(instance) < self.context.n_instances:
+            raise WaaError(1, f"instance {instance} out of range")
+        return self._inst_types.get(int(instance), self.type_)
+
+    @property
+    def per_instance(self) -> bool:
+        return bool(self._inst_types)
+
+    def _types_differ(self) -> bool:
+        return len({self.type_of(i) for i in range(self.context.n_instances)}) > 1 if self._inst_types else False
+
+    def _check_per_instance(self):
+        if self._types_differ() and self.context._b.prefix != "waa_":
+            raise WaaError(4, "one filter type per instance is a feature of the device library; this binding keeps one type "
+                              "per batch (render it one context at a time)")
 
     def _fill_desc(self, d):
         d.i[0] = BIQUAD_TYPE[self.type_]
+        if self.per_instance:
+            self._check_per_instance()  # (refusals before the batch exists)
+            if self.context._b.prefix != "waa_":
+                d.i[0] = BIQUAD_TYPE[self.type_of(0)]  # (equal types everywhere: the shared option)
 
-    def get_frequency_response(self, frequency_hz) -> tuple:
+    def _apply(self, ctx):
+        super()._apply(ctx)
+        if self.per_instance and ctx._b.prefix == "waa_":
+            b, h = ctx._b, ctx._handle
+            for i, t in sorted(self._inst_types.items()):
+                b.check(b.biquad_set_type_instance(h, self.id, i, BIQUAD_TYPE[t]))
+
+    def get_frequency_response(self, frequency_hz, instance: int = ALL) -> tuple:
+        """instance = i: the response of context i's filter — its type and its constants (or the ALL ones where it has none)"""
+        type_ = self.type_
+        pv = [p._const[ALL] for p in self.params]
+        if instance != ALL:
+            type_ = self.type_of(instance)
+            pv = [p._const.get(int(instance), p._const[ALL]) for p in self.params]
         hz = _f32(frequency_hz)
         mag = np.empty_like(hz)
         phase = np.empty_like(hz)
         b = self.context._b
-        b.check(b.biquad_frequency_response(BIQUAD_TYPE[self.type_], self.context.sample_rate, self.frequency.value,
-                                            self.detune.value, self.q.value, self.gain.value, _fp(hz), _fp(mag),
+        b.check(b.biquad_frequency_response(BIQUAD_TYPE[type_], self.context.sample_rate, pv[0], pv[1], pv[2], pv[3], _fp(hz), _fp(mag),
                                             _fp(phase), hz.size))
         return mag, phase
 

@@ -309,6 +309,24 @@ waa_status waa_iir_set_coefficients_instance(waa_batch* b, uint32_t node, uint32
   return WAA_OK;
 }
 
+// every context of the reference owns its BiquadFilterNode and sets its type (biquad_filter.rs:28-373, set_type :901-906): one
+// type for one instance; any number of calls, the last one wins
+waa_status waa_biquad_set_type_instance(waa_batch* b, uint32_t node, uint32_t inst, int32_t type) {
+  int e;
+  if ((e = check_node(b, node, WAA_NODE_BIQUAD)) || (e = check_unplanned(b))) return e;
+  if (inst != WAA_ALL_INSTANCES && inst >= b->n_inst)
+    return fail(WAA_ERR_INVALID_ARGUMENT, "instance %u out of range (BiquadFilterNode %u, %u instances)", inst, node, b->n_inst);
+  if (type < 0 || type > 7) return fail(WAA_ERR_INVALID_ARGUMENT, "bad biquad type");
+  Node& n = b->nodes[node];
+  if (inst == WAA_ALL_INSTANCES) {
+    n.desc.i[0] = type;  // (the shared type: instances with a type of their own keep it)
+    return WAA_OK;
+  }
+  if (!n.per_inst_type()) n.biquad_inst_type.assign(b->n_inst, (int8_t)-1);
+  n.biquad_inst_type[inst] = (int8_t)type;
+  return WAA_OK;
+}
+
 // AudioParam::set_value_at_time & co. (param.rs:428-596) on a param of the batch; evaluated at plan time
 waa_status waa_param_schedule_event(waa_batch* b, uint32_t node, uint32_t param, uint32_t inst, int32_t type, float value,
                                     double time, double aux, const float* curve, uint32_t n_curve) {

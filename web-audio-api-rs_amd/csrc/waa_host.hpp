@@ -212,6 +212,18 @@ struct Node {
   bool per_inst_iir() const { return !iir_inst_b.empty(); }
   const std::vector<double>& iir_b_of(uint32_t inst) const { return per_inst_iir() && !iir_inst_b[inst].empty() ? iir_inst_b[inst] : iir_b; }
   const std::vector<double>& iir_a_of(uint32_t inst) const { return per_inst_iir() && !iir_inst_b[inst].empty() ? iir_inst_a[inst] : iir_a; }
+  // biquad filter: one type per instance (waa_biquad_set_type_instance): [n_inst] once the first instance has its own type,
+  // -1 = that instance uses the shared one (desc.i[0]).  The planner asks types_differ(): a node whose instances all resolve to
+  // one type plans exactly as a shared node of that type (biquad_shared_type).
+  std::vector<int8_t> biquad_inst_type;
+  bool per_inst_type() const { return !biquad_inst_type.empty(); }
+  int biquad_type_of(uint32_t inst) const { return per_inst_type() && biquad_inst_type[inst] >= 0 ? biquad_inst_type[inst] : desc.i[0]; }
+  bool biquad_types_differ() const {
+    for (size_t i = 1; i < biquad_inst_type.size(); i++)
+      if (biquad_type_of((uint32_t)i) != biquad_type_of(0)) return true;
+    return false;
+  }
+  int biquad_shared_type() const { return per_inst_type() ? biquad_type_of(0) : desc.i[0]; }  // (only where !biquad_types_differ())
   // analyser (control side state): the pulls of ALL instances are computed by one launch and cached until the next render
   // (current_time after an offline render never changes: repeated pulls return the same data, analysis.rs:354-357)
   struct AnBatch {
@@ -364,6 +376,7 @@ struct Step {
   BiquadLanesDesc lanes{};  // BiquadTileDigest and BiquadLanes, waa_biquad_lanes.hip
   ConvDesc conv{};
   BiquadCoefDesc coef{};
+  const uint8_t* coef_types = nullptr;  // BiquadCoefs of a node whose instances differ in their filter type: [n_inst] on the device
   IirStreamDesc iir{};
   DelayDesc delay{};
   LoopDesc loop{};

@@ -669,6 +669,8 @@ struct BiquadCoefDesc {
   int32_t lane_major;   // element (tile, k, coef, lane) of frame tile * 2048 + lane * 32 + k
 };
 void launch_biquad_coefs(const BiquadCoefDesc& d, void* stream);
+// ... with one filter type per instance (biquad_coef_inst_kernel): types[d.rows] on the device, d.rows = n_inst, d.type unused
+void launch_biquad_coefs_inst(const BiquadCoefDesc& d, const uint8_t* types, void* stream);
 // A per-frame coefficient table that is the same for every instance is digested once per plan: for the 32 frames a
 // lane of the streaming kernel owns in a tile, the zero-state end state is LINEAR in the lane's samples,
 //   (y_31, y_30) = sum_i H_i x_i + Hm1 x_{-1} + Hm2 x_{-2},   H_i = G_i b0_i + G_{i+1} b1_{i+1} + G_{i+2} b2_{i+2},

@@ -81,6 +81,7 @@ static StepIo step_io_raw(const Step& st) {
       io_param(st.coef.detune, io);
       io_param(st.coef.q, io);
       io_param(st.coef.gain, io);
+      if (st.coef_types) io.reads.push_back(st.coef_types);  // one filter type per instance (uploaded at plan time)
       io.writes.push_back(st.coef.coefs);
       break;
     case StepKind::Timeline:

@@ -58,6 +58,7 @@ bool conv_fold_biquad_into_ir(const waa_batch* b, Node& conv, const Node& q) {
   // stage of conv_fft3_fwd_bq_kernel back; DESIGN.md section 5.9, INTEGRATION.md "runtime switches")
   if (getenv("WAA_NO_CONV_BIQUAD_IR_FOLD") || !conv.has_ir || q.params.size() < 4) return false;  // (read per plan: tests toggle it)
   if (conv.per_inst_ir()) return false;  // (one response per context: the fold into the forward transform does not look at H)
+  if (q.biquad_types_differ()) return false;  // (one type per context is per-context coefficients: the exact-order filter stage)
   float pv[4];
   for (int k = 0; k < 4; k++) {
     const ParamStore& ps = q.params[k];
@@ -66,7 +67,7 @@ bool conv_fold_biquad_into_ir(const waa_batch* b, Node& conv, const Node& q) {
       if (ps.cst[i] != ps.cst[0]) return false;  // (per-context coefficients: per-context responses — the kernel form keeps those)
     pv[k] = ps.fix(ps.cst[0]);
   }
-  const Coefs c = biquad_coefs(q.desc.i[0], (double)b->sr, (double)computed_freq(pv[WAA_PARAM_BIQUAD_FREQUENCY], pv[WAA_PARAM_BIQUAD_DETUNE]),
+  const Coefs c = biquad_coefs(q.biquad_shared_type(), (double)b->sr, (double)computed_freq(pv[WAA_PARAM_BIQUAD_FREQUENCY], pv[WAA_PARAM_BIQUAD_DETUNE]),
                                (double)pv[WAA_PARAM_BIQUAD_GAIN], (double)pv[WAA_PARAM_BIQUAD_Q]);
   for (double v : {c.b0, c.b1, c.b2, c.a1, c.a2})
     if (!std::isfinite(v)) return false;

@@ -11,6 +11,21 @@
 namespace waa {
 namespace host {
 
+// The plan's line for a BiquadFilterNode whose instances differ in their filter type: the node and the instances per type.  One
+// line per node, however often its ops are emitted.
+static void note_biquad_types(waa_batch* b, uint32_t id, const Node& n, const char* tail) {
+  static const char* const names[8] = {"lowpass", "highpass", "bandpass", "notch", "allpass", "peaking", "lowshelf", "highshelf"};
+  uint32_t cnt[8] = {};
+  for (uint32_t i = 0; i < b->n_inst; i++) cnt[n.biquad_type_of(i) & 7]++;
+  std::string line = "biquad node " + std::to_string(id) + ": one type per instance:";
+  for (int t = 0; t < 8; t++)
+    if (cnt[t]) line += std::string(" ") + names[t] + " x" + std::to_string(cnt[t]);
+  line += tail;
+  for (const std::string& l : b->plan_log)
+    if (l == line) return;
+  plan_note(b, "%s", line.c_str());
+}
+
 // Emit the fused ops of node `id` given the running channel count.
 int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector<OpDesc>& ops, int* out_nch) {
   Node& n = b->nodes[id];
@@ -75,13 +90,28 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
           for (uint32_t i = 1; i < b->n_inst && shared; i++) shared = ps.cst[i] == ps.cst[0];
           for (auto& blk : ps.blocks) shared &= blk.inst == WAA_ALL_INSTANCES;
         }
+        // one type per instance, and the types differ: a row per instance even under one shared automation — 40 B per frame
+        // and instance where the shared table is 40 B per frame (DESIGN.md 3.1 "Per-context types"; a row map over the at
+        // most eight distinct types would change every consumer kernel and is the follow-up)
+        const bool types_differ = n.biquad_types_differ();
+        const bool shared_params = shared;
+        if (types_differ) shared = false;
         cdsc.rows = shared ? 1u : b->n_inst;
-        cdsc.type = n.desc.i[0];
+        cdsc.type = types_differ ? -1 : n.biquad_shared_type();
         cdsc.sample_rate = b->sr;
+        if (types_differ) {
+          std::vector<uint8_t> types(b->n_inst);
+          for (uint32_t i = 0; i < b->n_inst; i++) types[i] = (uint8_t)n.biquad_type_of(i);
+          uint8_t* dty = nullptr;
+          if ((e = dev_upload(b, &dty, types))) return e;
+          cs.coef_types = dty;
+          cs.profile_slot = slot_for(b, "biquad_coef_inst_kernel");
+          note_biquad_types(b, id, n, shared_params ? "; a-rate: the coefficient table is per instance because of the types" : "; a-rate");
+        }
         double* dco = nullptr;
         if ((e = dev_alloc(b, &dco, (size_t)cdsc.rows * cdsc.frames_padded * 5))) return e;
         cdsc.coefs = dco;
-        cs.profile_slot = slot_for(b, "biquad_coef_kernel");
+        if (!types_differ) cs.profile_slot = slot_for(b, "biquad_coef_kernel");
         b->steps.push_back(cs);
         double* dst = nullptr;
         if ((e = dev_alloc(b, &dst, (size_t)b->n_inst * STATE_STRIDE))) return e;
@@ -103,13 +133,18 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
       }
       const uint64_t per = varies ? (uint64_t)b->n_quanta * 5 : 5;
       std::vector<double> co((size_t)b->n_inst * per);
-      std::vector<float> pf, pd, pq, pg;  // the previous instance's values: the same values give the same coefficient row
+      std::vector<float> pf, pd, pq, pg;  // the previous instance's values and type: the same values give the same coefficient row
+      int ptype = -1;
+      // one type per instance: every row from its instance's type.  This is the only builder of these rows — the stream, scan, row,
+      // dyn, loop and echo kernels all read what is uploaded here.  Equal types everywhere: the rows of a shared node of that type.
+      if (n.biquad_types_differ()) note_biquad_types(b, id, n, "");
       for (uint32_t i = 0; i < b->n_inst; i++) {
+        const int type = n.biquad_type_of(i);
         auto f = param_per_quantum(b, n.params[WAA_PARAM_BIQUAD_FREQUENCY], i, nullptr);
         auto d = param_per_quantum(b, n.params[WAA_PARAM_BIQUAD_DETUNE], i, nullptr);
         auto q = param_per_quantum(b, n.params[WAA_PARAM_BIQUAD_Q], i, nullptr);
         auto g = param_per_quantum(b, n.params[WAA_PARAM_BIQUAD_GAIN], i, nullptr);
-        if (i > 0 && f == pf && d == pd && q == pq && g == pg) {
+        if (i > 0 && type == ptype && f == pf && d == pd && q == pq && g == pg) {
           // (one k-rate sweep for all 1024 contexts: 3.8 M coefficient sets — sin, cos, pow each — were 0.7 s of the plan)
           std::copy(co.begin() + (size_t)(i - 1) * per, co.begin() + (size_t)i * per, co.begin() + (size_t)i * per);
           continue;
@@ -118,10 +153,11 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
         pd = d;
         pq = q;
         pg = g;
+        ptype = type;
         const uint32_t cnt = varies ? b->n_quanta : 1;
         for (uint32_t k = 0; k < cnt; k++) {
           auto at = [&](const std::vector<float>& v) { return v[v.size() == 1 ? 0 : k]; };
-          Coefs c = biquad_coefs(n.desc.i[0], (double)b->sr, (double)computed_freq(at(f), at(d)), (double)at(g), (double)at(q));
+          Coefs c = biquad_coefs(type, (double)b->sr, (double)computed_freq(at(f), at(d)), (double)at(g), (double)at(q));
           double* dst = &co[(size_t)i * per + (size_t)k * 5];
           dst[0] = c.b0;
           dst[1] = c.b1;

@@ -65,7 +65,9 @@ static int run_step(waa_batch* b, const Step& st, uint32_t t0, uint32_t t1) {
       if (d.kb1 <= d.kb0) return 0;
       return launch_whole(b, st.slot_mac, d, d.per_inst ? launch_conv_inst_direct : launch_conv_direct);
     }
-    case StepKind::BiquadCoefs: return launch_whole(b, slot, st.coef, launch_biquad_coefs);
+    case StepKind::BiquadCoefs:
+      if (st.coef_types) return timed(b, slot, [&] { launch_biquad_coefs_inst(st.coef, st.coef_types, b->stream); });
+      return launch_whole(b, slot, st.coef, launch_biquad_coefs);
     case StepKind::IirStream: return launch_tiles(b, slot, st.iir, t0, t1, launch_iir_stream);
     case StepKind::Delay: return launch_tiles(b, slot, st.delay, t0, t1, launch_delay);
     case StepKind::Loop: return launch_whole(b, slot, st.loop, launch_loop);

@@ -8,7 +8,7 @@ step for the Python mirror (round-5 review, missing 4): contexts built one by on
 channel configuration, connections), the context's format, the SHAPES of per-context payloads (an AudioBufferSource's channel count,
 length and rate, and on the device library the padded length of an IIRFilterNode's coefficients, which become per-instance sets of the
 batch) and the identity of payloads a batch shares (a convolver's impulse response, an oversampled shaper's curve, and on other bindings
-IIR coefficients, an oscillator's PeriodicWave and a plain shaper's curve, which the device library takes per instance) — every bucket is merged into one
+IIR coefficients, an oscillator's PeriodicWave, a plain shaper's curve and a Biquad's type, which the device library takes per instance) — every bucket is merged into one
 batch (per-context AudioBuffers, AudioParam values and automation, start / stop / loop settings become per-instance settings of the batch), rendered, and the AudioBuffers are handed back in the callers' order.
 Contexts with suspend callbacks render on their own (their callbacks may do anything)."""
 from __future__ import annotations
@@ -18,7 +18,7 @@ from typing import List, Sequence
 
 import numpy as np
 
-from .api import ALL, AudioBufferSourceNode, AudioParam, ConvolverNode, IIRFilterNode, OfflineAudioContext, OscillatorNode, RenderedBatch, \
+from .api import ALL, AudioBufferSourceNode, AudioParam, BiquadFilterNode, ConvolverNode, IIRFilterNode, OfflineAudioContext, OscillatorNode, RenderedBatch, \
     WaveShaperNode, _ScheduledSource
 
 
@@ -48,8 +48,12 @@ def _wave_id(w) -> tuple:
 
 def _node_key(nd) -> tuple:
     d = nd._desc()
+    ints = tuple(int(x) for x in d.i)
+    if isinstance(nd, BiquadFilterNode) and nd.context._b.prefix == "waa_":
+        # the device library takes one filter type per context: contexts that differ only in their Biquad's type share a batch
+        ints = ("biquad-type",) + ints[1:]
     key = [type(nd).__name__, int(d.kind), int(d.channel_count), int(d.channel_count_mode), int(d.channel_interpretation),
-           tuple(int(x) for x in d.i), tuple(float(x) for x in d.d)]
+           ints, tuple(float(x) for x in d.d)]
     if isinstance(nd, ConvolverNode):  # (shared by the batch: another response is another batch)
         key.append(None if nd.buffer is None else (_digest(nd.buffer.data), float(nd.buffer.sample_rate)))
         pcm = getattr(nd, "_pcm", None)
@@ -147,6 +151,14 @@ def _merge(bucket: Sequence[OfflineAudioContext]) -> OfflineAudioContext:
             if not all(np.array_equal(ff, sets[0][0]) and np.array_equal(fb, sets[0][1]) for ff, fb in sets[1:]):
                 for i, (ff, fb) in enumerate(sets[1:], start=1):
                     cn.set_coefficients(ff, fb, instance=i)
+        if isinstance(cn, BiquadFilterNode):
+            # every context's effective type becomes its instance's; equal types everywhere: the node stays shared
+            types = [nd.type_of(0) for nd in [cn] + others]
+            cn._inst_types = {}
+            cn.type_ = types[0]
+            if not all(t == types[0] for t in types[1:]):
+                for i, t in enumerate(types):
+                    cn.set_type(t, instance=i)
         if isinstance(cn, WaveShaperNode) and _curve(cn) is not None:
             # every context's effective curve (_curve) becomes its instance's; equal curves everywhere: the node stays shared
             curves = [_curve(nd) for nd in [cn] + others]
