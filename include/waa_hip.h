@@ -471,8 +471,9 @@ typedef struct waa_sharded_job {
                                   * values rendered from the sub-batch's own audio (waa_batch_rearm).  A `setup` that hands
                                   * every sub-batch its own slice [first, first + count) of per-instance impulse responses
                                   * (CONVOLVER i[1] = 1), of per-instance IIR coefficient sets, of per-instance WaveShaper curves or
-                                  * of per-instance Biquad types (waa_iir_set_coefficients_instance,
-                                  * waa_waveshaper_set_curve_instance, waa_biquad_set_type_instance, waa_hip_device.h)
+                                  * of per-instance Biquad or Oscillator types (waa_iir_set_coefficients_instance,
+                                  * waa_waveshaper_set_curve_instance, waa_biquad_set_type_instance,
+                                  * waa_oscillator_set_type_instance, waa_hip_device.h)
                                   * depends on `first`: leave this 0 there */
 } waa_sharded_job;
 /* Blocks until every context is rendered and downloaded; *seconds (may be NULL) = wall time.  Pinned host buffers let

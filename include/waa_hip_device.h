@@ -100,6 +100,37 @@ waa_status waa_waveshaper_set_curve_instance(waa_batch* batch, uint32_t node, ui
  * but the audio. */
 waa_status waa_biquad_set_type_instance(waa_batch* batch, uint32_t node, uint32_t instance, int32_t type);
 
+/* OscillatorNode::set_type of ONE context of the batch (src/node/oscillator.rs:305-330): in the reference every context owns its
+ * OscillatorNode and sets its type.  Replaces one batch, one plan and one launch sequence per waveform (up to five): a data set
+ * of synthetic notes, each with a random waveform, pitch, detune and envelope.  Frequency, detune, start / stop and the
+ * PeriodicWave were per instance already.
+ *
+ * type: WAA_OSC_SINE .. WAA_OSC_TRIANGLE.  WAA_OSC_CUSTOM is "InvalidStateError: Custom type cannot be set manually", as in the
+ * reference; anything else is "bad oscillator type" (WAA_ERR_INVALID_ARGUMENT).  Refused once the batch is planned
+ * (InvalidStateError), for an instance >= n_instances and for a node of another kind (WAA_ERR_INVALID_ARGUMENT).
+ * instance = WAA_ALL_INSTANCES sets the node's shared type (i[0]).  A later call for the same instance replaces the earlier one.
+ *
+ * The type instance i renders with is resolved when the batch is planned, in this order:
+ *   1. i has a PeriodicWave of its own (waa_oscillator_set_periodic_wave_instance / _set_wavetable_instance): custom, with that
+ *      wave; a type set for i is ignored, as the reference ignores set_type on a node that has a wave (:321-324);
+ *   2. i has a type of its own: that type, EVEN WHERE A SHARED WAVE EXISTS.  Everywhere in this interface the values given for
+ *      WAA_ALL_INSTANCES are defaults for the contexts without a setting of their own; this is the one place where a batch is
+ *      therefore not literally "every context made the ALL call" (such a context would be custom);
+ *   3. a shared wave exists: custom, with it;
+ *   4. the node has per-instance waves but no shared one, and i has neither a wave nor a type: the plan fails,
+ *      "InvalidStateError - OscillatorNode N has no PeriodicWave for instance k";
+ *   5. otherwise the node's shared type (i[0]).
+ * waa_oscillator_get_wavetable of an instance that resolves to a built-in type is InvalidStateError ("has no PeriodicWave").
+ *
+ * A node whose instances all resolve to the same type plans and renders exactly as today (the same kernels, uploads and plan
+ * text).  Where they differ, the plan uploads a type byte per instance, the 2048-point sine table and table rows for the custom
+ * instances alone, and the one Osc step is rendered by the kernels of waa_osc_types.hip, which read the type per instance and
+ * otherwise are the single-type kernels (one launch for the time-parallel form, two passes for the prefix-sum form): every
+ * instance gets the bits a batch of its type alone gives it.  The post-gain, LFO and two-operator FM folds carry the types.
+ * Called at a suspend point it applies to the whole render, like the shared option.  waa_batch_rearm
+ * keeps the types, like everything but the audio. */
+waa_status waa_oscillator_set_type_instance(waa_batch* batch, uint32_t node, uint32_t instance, int32_t type);
+
 #ifdef __cplusplus
 }
 #endif

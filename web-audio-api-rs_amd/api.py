@@ -208,6 +208,7 @@ ABI_DEVICE = {
     "oscillator_get_wavetable": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, C.c_uint32]),
     "waveshaper_set_curve_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, C.c_uint32]),
     "biquad_set_type_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, C.c_int32]),
+    "oscillator_set_type_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, C.c_int32]),
 }
 
 
@@ -685,15 +686,54 @@ class OscillatorNode(_ScheduledSource):
         self.params = [self.frequency, self.detune]
         self.periodic_wave = None
         self._inst_waves = {}  # instance -> PeriodicWave: one wave per context (waa_oscillator_set_periodic_wave_instance)
+        self._inst_types = {}  # instance -> built-in type name: one type per context (waa_oscillator_set_type_instance)
         if periodic_wave is not None:
             self.set_periodic_wave(periodic_wave)
 
-    def set_type(self, type_: str):
+    def set_type(self, type_: str, instance: int = ALL):
+        """instance = ALL: the node's type, as before (ignored once the node is custom).  instance = i: context i's own built-in
+        type (every context of the reference sets the type of its own node, oscillator.rs:305-330); the last call for an instance
+        wins.  What a context renders with: type_of."""
         if type_ == "custom":  # oscillator.rs:305-309
             raise WaaError(3, "InvalidStateError: Custom type cannot be set manually")
-        if self.type_ == "custom":  # ignored once a periodic wave is set (oscillator.rs:311-314)
-            return
-        self.type_ = type_
+        if instance == ALL:
+            if self.type_ != "custom":  # ignored once a periodic wave is set (oscillator.rs:311-314)
+                self.type_ = type_
+            return self
+        if type_ not in OSCILLATOR_TYPE:
+            raise WaaError(1, "bad oscillator type")
+        if self.context._handle is not None:
+            raise WaaError(3, "InvalidStateError - the batch is frozen once rendering has started")
+        if not 0 <= int(instance) < self.context.n_instances:
+            raise WaaError(1, f"instance {instance} out of range")
+        self._inst_types[int(instance)] = type_
+        return self
+
+    def set_type_batch(self, types):
+        """types: a sequence of n_instances built-in type names, one per context"""
+        n = self.context.n_instances
+        if len(types) != n:
+            raise WaaError(1, f"set_type_batch takes n_instances = {n} types, got {len(types)}")
+        for i, t in enumerate(types):
+            self.set_type(t, instance=i)
+        return self
+
+    def type_of(self, instance: int) -> str:
+        """The type context `instance` renders with, resolved as the device library's plan resolves it: its own PeriodicWave
+        (custom; a type given to it is ignored), its own type (also where a shared wave exists), the shared wave (custom), the
+        node's type.  A node with per-instance waves, no shared one and nothing for this instance: WaaError(3), the plan's refusal."""
+        if not 0 <= int(instance) < self.context.n_instances:
+            raise WaaError(1, f"instance {instance} out of range")
+        i = int(instance)
+        if i in self._inst_waves:
+            return "custom"
+        if i in self._inst_types:
+            return self._inst_types[i]
+        if self.periodic_wave is not None:
+            return "custom"
+        if self._inst_waves:
+            raise WaaError(3, f"InvalidStateError - OscillatorNode {self.id} has no PeriodicWave for instance {i}")
+        return self.type_
 
     def set_periodic_wave(self, wave: PeriodicWave, instance: int = ALL):
         """instance = ALL: the wave of every context without one of its own.  instance = i: context i's own PeriodicWave (coefficients
@@ -733,6 +773,12 @@ class OscillatorNode(_ScheduledSource):
             raise WaaError(4, "one PeriodicWave per instance is a feature of the device library; this binding keeps one wave "
                               "per batch (render it one context at a time)")
 
+    def _check_per_instance_types(self):
+        """another binding keeps one type per batch: types that all resolve equal go through as the shared option"""
+        if self.context._b.prefix != "waa_" and len({self.type_of(i) for i in range(self.context.n_instances)}) > 1:
+            raise WaaError(4, "one oscillator type per instance is a feature of the device library; this binding keeps one type "
+                              "per batch (render it one context at a time)")
+
     def wavetable(self, instance: int = 0) -> np.ndarray:
         """The 8192-point table context `instance` renders with.  A node in per-instance mode is planned first (which freezes the
         batch): the answer is then the instance's row of the device's tables; otherwise, and on a plan-only context, the table
@@ -753,6 +799,10 @@ class OscillatorNode(_ScheduledSource):
         d.i[0] = OSCILLATOR_TYPE[self.type_]
         if self.per_instance:
             self._check_per_instance()  # (refusals before the batch exists)
+        if self._inst_types:
+            self._check_per_instance_types()
+            if self.context._b.prefix != "waa_" and self.type_of(0) != "custom":
+                d.i[0] = OSCILLATOR_TYPE[self.type_of(0)]  # (equal types everywhere: the shared option)
 
     @staticmethod
     def _set_wave(b, h, node, w, *inst):
@@ -766,9 +816,15 @@ class OscillatorNode(_ScheduledSource):
     def _apply(self, ctx):
         super()._apply(ctx)
         b, h = ctx._b, ctx._handle
-        if self.periodic_wave is not None:
+        # another binding with own types: they are all equal (_fill_desc) and went through as the shared option; where that type is
+        # built-in it outranks a shared wave in every context, so no wave is sent
+        send_waves = not (self._inst_types and b.prefix != "waa_" and self.type_of(0) != "custom")
+        if self._inst_types and b.prefix == "waa_":
+            for i, t in sorted(self._inst_types.items()):
+                b.check(b.oscillator_set_type_instance(h, self.id, i, OSCILLATOR_TYPE[t]))
+        if send_waves and self.periodic_wave is not None:
             self._set_wave(b, h, self.id, self.periodic_wave)
-        if self.per_instance:
+        if send_waves and self.per_instance:
             self._check_per_instance()
             for i, w in sorted(self._inst_waves.items()):
                 self._set_wave(b, h, self.id, w, i)

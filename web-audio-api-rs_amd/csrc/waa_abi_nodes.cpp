@@ -225,6 +225,25 @@ waa_status waa_oscillator_set_wavetable_instance(waa_batch* b, uint32_t node, ui
   return WAA_OK;
 }
 
+// every context of the reference owns its OscillatorNode and calls set_type on it (oscillator.rs:305-330): one built-in type for one
+// instance; any number of calls, the last one wins.  An instance with a PeriodicWave of its own stays custom (Node::osc_type_of)
+waa_status waa_oscillator_set_type_instance(waa_batch* b, uint32_t node, uint32_t inst, int32_t type) {
+  int e;
+  if ((e = check_node(b, node, WAA_NODE_OSCILLATOR)) || (e = check_unplanned(b))) return e;
+  if (inst != WAA_ALL_INSTANCES && inst >= b->n_inst)
+    return fail(WAA_ERR_INVALID_ARGUMENT, "instance %u out of range (OscillatorNode %u, %u instances)", inst, node, b->n_inst);
+  if (type < WAA_OSC_SINE || type > WAA_OSC_CUSTOM) return fail(WAA_ERR_INVALID_ARGUMENT, "bad oscillator type");
+  if (type == WAA_OSC_CUSTOM) return fail(WAA_ERR_INVALID_STATE, "InvalidStateError: Custom type cannot be set manually");
+  Node& n = b->nodes[node];
+  if (inst == WAA_ALL_INSTANCES) {
+    n.desc.i[0] = type;  // (the shared type: instances with a type or a wave of their own keep it)
+    return WAA_OK;
+  }
+  if (n.osc_inst_type.empty()) n.osc_inst_type.assign(b->n_inst, (int8_t)-1);
+  n.osc_inst_type[inst] = (int8_t)type;
+  return WAA_OK;
+}
+
 // the table an instance renders with: its row of the plan's tables once they exist, the host's table otherwise
 waa_status waa_oscillator_get_wavetable(waa_batch* b, uint32_t node, uint32_t inst, float* out, uint32_t n) {
   int e;
@@ -234,7 +253,9 @@ waa_status waa_oscillator_get_wavetable(waa_batch* b, uint32_t node, uint32_t in
   if (!out || n != WAA_PERIODIC_WAVE_TABLE_LENGTH)
     return fail(WAA_ERR_INVALID_ARGUMENT, "IndexSizeError - a PeriodicWave table has %d points (got %u)", WAA_PERIODIC_WAVE_TABLE_LENGTH, n);
   const Node& nd = b->nodes[node];
-  if (nd.per_inst_wave() && b->planned && !b->dry && nd.d_osc_tables) {
+  if (nd.osc_type_of(inst) != WAA_OSC_CUSTOM)  // (a built-in type, its own or the shared one)
+    return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - oscillator %u has no PeriodicWave for instance %u", node, inst);
+  if (nd.d_osc_row && b->planned && !b->dry && nd.d_osc_tables) {
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipStreamSynchronize(b->stream));  // (the generator runs on the batch's stream)
     uint32_t row = 0;

@@ -204,6 +204,17 @@ struct Node {
   float* d_osc_tables = nullptr;
   uint32_t* d_osc_row = nullptr;
   uint32_t osc_rows = 0, osc_gen_rows = 0;
+  // one built-in type per instance (waa_oscillator_set_type_instance): [n_inst] once the first instance has its own type, -1 = none.
+  // osc_type_of: the type an instance renders with (the order of waa_hip_device.h): its own wave, its own type, the shared wave,
+  // -1 where the node has per-instance waves and this instance nothing (build_plan refuses), else the shared type (desc.i[0])
+  std::vector<int8_t> osc_inst_type;
+  int osc_type_of(uint32_t inst) const {
+    if (per_inst_wave() && osc_inst[inst].own()) return WAA_OSC_CUSTOM;
+    if (!osc_inst_type.empty() && osc_inst_type[inst] >= 0) return osc_inst_type[inst];
+    if (!osc_wave.empty()) return WAA_OSC_CUSTOM;
+    if (per_inst_wave()) return -1;
+    return desc.i[0];
+  }
   // iir filter: normalised coefficient pairs (iir_filter.rs:273-311)
   std::vector<double> iir_b, iir_a;
   // one set per instance (waa_iir_set_coefficients_instance): [n_inst] once the first instance has its own set, normalised like

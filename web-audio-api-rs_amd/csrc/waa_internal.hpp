@@ -473,6 +473,16 @@ struct OscDesc {
   int32_t pa_on;
   float pa_min, pa_max, pa_default;
   ParamRef pa_intrinsic;          // mode 0 / 1
+  // One type per instance (waa_oscillator_set_type_instance, instances that resolve to different types; waa_osc_types.hip):
+  // non-null `type_inst` = [n_inst] WAA_OSC_* bytes.  `type` is then unused, `sine_table` the 2048-point sine, `table` the custom
+  // instances' [rows][8192] with `wave_row` for every instance (0 for one that is not custom; both null without a custom instance).
+  // fm_type_inst / fm_sine_table: the same of a folded modulator (fm_table / fm_wave_row its rows).  Either may be null on its own.
+  const uint8_t* type_inst;
+  const float* sine_table;
+  const uint8_t* fm_type_inst;
+  const float* fm_sine_table;
+  int32_t any_custom;             // a custom instance exists: the time-parallel kernel gets 32 KB of LDS to stage a row in
+  int32_t sine_in_lds;            // set by launch_osc_types: sine instances stage the sine table in LDS (off: an A/B switch)
 };
 constexpr int OSC_SEGMENTS = 8;  // time segments per instance of the prefix-sum oscillator (one wavefront each)
 // Per-(instance, quantum) record of the time-parallel oscillator: frames [first, end) of the quantum are active,
@@ -484,6 +494,7 @@ struct OscQuantum {
   int32_t outside_nyquist;
 };
 void launch_osc(const OscDesc& d, void* stream);
+void launch_osc_types(const OscDesc& d, void* stream);  // (through launch_osc)
 
 // ---- PeriodicWave tables on the device (periodic_wave.rs:164-189; waa_periodic_wave.hip) --------------
 // One workgroup per distinct coefficient set: 8192 entries in the reference's f32 order, max |sample| through LDS, scaled by

@@ -1375,7 +1375,7 @@ static int build_plan_impl(waa_batch* b) {
     const Node& n = b->nodes[i];
     if (n.desc.kind != WAA_NODE_OSCILLATOR || !n.per_inst_wave() || !n.osc_wave.empty()) continue;
     for (uint32_t inst = 0; inst < b->n_inst; inst++)
-      if (!n.osc_inst[inst].own())
+      if (n.osc_type_of(inst) < 0)  // (neither a wave nor a built-in type of its own)
         return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - OscillatorNode %u has no PeriodicWave for instance %u", i, inst);
   }
   // processing order = reversed DFS post-order over outgoing edges in insertion order, cycle breakers applied

@@ -307,11 +307,18 @@ static inline bool osc_quantum_fully_active(double block_time, double next_block
 // uploaded into their rows; the rows of coefficient sets are generated by ONE launch of waa_periodic_wave.hip on the batch's
 // stream, here and not in the render's launch list: the tables depend on nothing a render or a re-arm changes.  They are made
 // once per batch (a second planning pass finds them in place).
-static int plan_periodic_wave_rows(waa_batch* b, uint32_t id) {
+// `types` (a node whose instances resolve to different types, plan_oscillator): only the custom instances get rows; the others'
+// entry of the row index is 0 and never read.
+static int plan_periodic_wave_rows(waa_batch* b, uint32_t id, const std::vector<uint8_t>* types = nullptr) {
   Node& n = b->nodes[id];
-  uint32_t n_max = 2;
+  static const Node::OscWave no_wave;
+  auto wave_of = [&](uint32_t i) -> const Node::OscWave& { return n.per_inst_wave() ? n.osc_inst[i] : no_wave; };
+  auto custom = [&](uint32_t i) { return !types || (*types)[i] == WAA_OSC_CUSTOM; };
+  uint32_t n_max = 2, n_custom = 0;
   for (uint32_t i = 0; i < b->n_inst; i++) {
-    const Node::OscWave& w = n.osc_inst[i];
+    if (!custom(i)) continue;
+    n_custom++;
+    const Node::OscWave& w = wave_of(i);
     if (!w.own() && n.osc_wave.empty()) return fail(WAA_ERR_INVALID_STATE, "internal: OscillatorNode %u, instance %u without a PeriodicWave got past build_plan", id, i);
     n_max = std::max<uint32_t>(n_max, (uint32_t)w.real.size());
   }
@@ -323,7 +330,8 @@ static int plan_periodic_wave_rows(waa_batch* b, uint32_t id) {
     std::vector<std::pair<uint32_t, const std::vector<float>*>> uploads;  // (row, finished table)
     std::string key;
     for (uint32_t i = 0; i < b->n_inst; i++) {
-      const Node::OscWave& w = n.osc_inst[i];
+      if (!custom(i)) continue;  // (row_of[i] stays 0)
+      const Node::OscWave& w = wave_of(i);
       const bool coefs = !w.real.empty();
       const std::vector<float>& table = w.own() ? w.table : n.osc_wave;
       key.assign(1, coefs ? (w.no_norm ? 'u' : 'n') : 't');
@@ -392,7 +400,7 @@ static int plan_periodic_wave_rows(waa_batch* b, uint32_t id) {
     n.osc_gen_rows = (uint32_t)gen_dst.size();
   }
   plan_note(b, "oscillator node %u: one PeriodicWave per instance: %u table row(s) for %u instance(s), %u generated on the device (coefficient sets padded to %u), %u uploaded",
-            id, n.osc_rows, b->n_inst, n.osc_gen_rows, n_max, n.osc_rows - n.osc_gen_rows);
+            id, n.osc_rows, n_custom, n.osc_gen_rows, n_max, n.osc_rows - n.osc_gen_rows);
   return 0;
 }
 
@@ -417,23 +425,46 @@ int plan_oscillator(waa_batch* b, uint32_t id) {
   if ((e = dev_upload(b, &d_start, start)) || (e = dev_upload(b, &d_stop, stop))) return e;
   d.start = d_start;
   d.stop = d_stop;
-  d.type = n.osc_wave.empty() && !n.per_inst_wave() ? n.desc.i[0] : WAA_OSC_CUSTOM;
-  if (d.type == WAA_OSC_CUSTOM && n.osc_wave.empty() && !n.per_inst_wave())
-    return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - custom oscillator %u has no PeriodicWave", id);
-  if (n.per_inst_wave()) {
+  // the type every instance renders with (Node::osc_type_of).  All alike — the usual node, also one whose instances were all
+  // given the same type — plans as a node of that one type; only where they differ do the kernels read a type per instance
+  std::vector<uint8_t> types(b->n_inst);
+  uint32_t type_count[5] = {0, 0, 0, 0, 0};
+  for (uint32_t i = 0; i < b->n_inst; i++) {
+    const int t = n.osc_type_of(i);
+    if (t < 0) return fail(WAA_ERR_INVALID_STATE, "internal: OscillatorNode %u, instance %u without a PeriodicWave got past build_plan", id, i);
+    if (t == WAA_OSC_CUSTOM && n.osc_wave.empty() && !(n.per_inst_wave() && n.osc_inst[i].own()))
+      return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - custom oscillator %u has no PeriodicWave", id);
+    types[i] = (uint8_t)t;
+    type_count[t]++;
+  }
+  const bool mixed = type_count[types[0]] != b->n_inst;
+  d.type = mixed ? -1 : (int32_t)types[0];
+  auto sine_table = [] {  // oscillator.rs:16-28 (same libm sinf as the reference's f32::sin)
+    std::vector<float> table(2048);
+    const float pi = 3.14159265358979323846f;
+    for (int x = 0; x < 2048; x++) table[x] = std::sin(((float)x) * 2.0f * pi * (1.f / 2048.f));
+    return table;
+  };
+  if (mixed) {
+    uint8_t* d_types = nullptr;
+    float* d_sine = nullptr;
+    if ((e = dev_upload(b, &d_types, types)) || (e = dev_upload(b, &d_sine, sine_table()))) return e;
+    d.type_inst = d_types;
+    d.sine_table = d_sine;
+    d.table_len = PERIODIC_WAVE_LEN;
+    if (type_count[WAA_OSC_CUSTOM]) {  // rows for the custom instances alone
+      if ((e = plan_periodic_wave_rows(b, id, &types))) return e;
+      d.table = n.d_osc_tables;
+      d.wave_row = n.d_osc_row;
+      d.any_custom = 1;
+    }
+  } else if (d.type == WAA_OSC_CUSTOM && n.per_inst_wave()) {
     if ((e = plan_periodic_wave_rows(b, id))) return e;
     d.table = n.d_osc_tables;
     d.wave_row = n.d_osc_row;
     d.table_len = PERIODIC_WAVE_LEN;
   } else {
-    std::vector<float> table;
-    if (d.type == WAA_OSC_CUSTOM) {
-      table = n.osc_wave;
-    } else {  // oscillator.rs:16-28 (same libm sinf as the reference's f32::sin)
-      table.resize(2048);
-      const float pi = 3.14159265358979323846f;
-      for (int x = 0; x < 2048; x++) table[x] = std::sin(((float)x) * 2.0f * pi * (1.f / 2048.f));
-    }
+    const std::vector<float> table = d.type == WAA_OSC_CUSTOM ? n.osc_wave : sine_table();
     float* d_table = nullptr;
     if ((e = dev_upload(b, &d_table, table))) return e;
     d.table = d_table;
@@ -610,7 +641,15 @@ int plan_oscillator(waa_batch* b, uint32_t id) {
   n.osc_step = (parallel || scan) ? (int)b->steps.size() : -1;  // (the serial cross-check kernel takes no post ops)
   b->steps.push_back(st);
   static const char* names[] = {"sine", "square", "sawtooth", "triangle", "custom"};
-  plan_note(b, "oscillator node %u: %s (%s) frequency=%s detune=%s", id, names[d.type],
+  std::string what;
+  if (mixed) {
+    what = "one type per instance:";
+    for (int t = 0; t < 5; t++)
+      if (type_count[t]) what += std::string(" ") + names[t] + " x" + std::to_string(type_count[t]);
+  } else {
+    what = names[d.type];
+  }
+  plan_note(b, "oscillator node %u: %s (%s) frequency=%s detune=%s", id, what.c_str(),
             parallel ? "time-parallel, closed-form phase" : scan ? "prefix-sum phase" : "lane per instance, serial phase",
             d.frequency.mode == 0 ? "const" : d.frequency.mode == 1 ? "k-rate" : "a-rate",
             d.detune.mode == 0 ? "const" : d.detune.mode == 1 ? "k-rate" : "a-rate");
@@ -671,6 +710,8 @@ void fuse_fm_operators(waa_batch* b) {
     d.fm_wave_row = ms.osc.wave_row;  // (a modulator with one PeriodicWave per instance: the carrier looks its row up like the modulator would)
     d.fm_table_len = ms.osc.table_len;
     d.fm_type = ms.osc.type;
+    d.fm_type_inst = ms.osc.type_inst;  // (a modulator with one type per instance: the carrier's kernel reads its bytes, waa_osc_types.hip)
+    d.fm_sine_table = ms.osc.sine_table;
     d.fm_has_gain = ch.in[0].has_gain ? 1 : 0;
     d.fm_gain = ch.in[0].gain;
     std::memcpy(&d.fm_min, &ch.ops[0].i0, 4);

@@ -8,7 +8,7 @@ step for the Python mirror (round-5 review, missing 4): contexts built one by on
 channel configuration, connections), the context's format, the SHAPES of per-context payloads (an AudioBufferSource's channel count,
 length and rate, and on the device library the padded length of an IIRFilterNode's coefficients, which become per-instance sets of the
 batch) and the identity of payloads a batch shares (a convolver's impulse response, an oversampled shaper's curve, and on other bindings
-IIR coefficients, an oscillator's PeriodicWave, a plain shaper's curve and a Biquad's type, which the device library takes per instance) — every bucket is merged into one
+IIR coefficients, an oscillator's PeriodicWave and built-in type, a plain shaper's curve and a Biquad's type, which the device library takes per instance) — every bucket is merged into one
 batch (per-context AudioBuffers, AudioParam values and automation, start / stop / loop settings become per-instance settings of the batch), rendered, and the AudioBuffers are handed back in the callers' order.
 Contexts with suspend callbacks render on their own (their callbacks may do anything)."""
 from __future__ import annotations
@@ -52,6 +52,9 @@ def _node_key(nd) -> tuple:
     if isinstance(nd, BiquadFilterNode) and nd.context._b.prefix == "waa_":
         # the device library takes one filter type per context: contexts that differ only in their Biquad's type share a batch
         ints = ("biquad-type",) + ints[1:]
+    if isinstance(nd, OscillatorNode) and nd.context._b.prefix == "waa_" and nd.type_of(0) != "custom":
+        # ... and one built-in oscillator type per context; a context with a PeriodicWave stays apart from one without (below)
+        ints = ("oscillator-type",) + ints[1:]
     key = [type(nd).__name__, int(d.kind), int(d.channel_count), int(d.channel_count_mode), int(d.channel_interpretation),
            ints, tuple(float(x) for x in d.d)]
     if isinstance(nd, ConvolverNode):  # (shared by the batch: another response is another batch)
@@ -74,7 +77,7 @@ def _node_key(nd) -> tuple:
             key.append(("iir-len", max(ff.size, fb.size)))
         else:
             key.append((_digest(ff), _digest(fb)))
-    if isinstance(nd, OscillatorNode) and _osc_wave(nd) is not None:
+    if isinstance(nd, OscillatorNode) and nd.type_of(0) == "custom":
         if nd.context._b.prefix == "waa_":
             # the device library takes one PeriodicWave per context: contexts that differ only in their waves share a batch
             key.append("periodic-wave")
@@ -168,7 +171,16 @@ def _merge(bucket: Sequence[OfflineAudioContext]) -> OfflineAudioContext:
                 cn.curve = None
                 for i, c in enumerate(curves):
                     cn.set_curve(c, instance=i)
-        if isinstance(cn, OscillatorNode) and _osc_wave(cn) is not None:
+        if isinstance(cn, OscillatorNode) and cn.type_of(0) != "custom":
+            # every context's effective built-in type becomes its instance's; equal types everywhere: the node stays shared
+            types = [nd.type_of(0) for nd in [cn] + others]
+            cn._inst_types = {}
+            cn.periodic_wave = None  # (a shared wave that context 0's own type outranked: nobody renders with it)
+            cn.type_ = types[0]
+            if not all(t == types[0] for t in types[1:]):
+                for i, t in enumerate(types):
+                    cn.set_type(t, instance=i)
+        if isinstance(cn, OscillatorNode) and cn.type_of(0) == "custom":
             # every context's effective wave (_osc_wave) becomes its instance's; equal waves everywhere: the node stays shared
             waves = [_osc_wave(nd) for nd in [cn] + others]
             cn._inst_waves = {}
