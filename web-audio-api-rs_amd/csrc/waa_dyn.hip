@@ -12,6 +12,13 @@
 // signal accompanied by a per-quantum code = count | CODE_SILENT.  Feedback loops need nothing extra in this form
 // (the loop kernel of waa_loop.hip is the static-count special case).  Latency-bound by construction; throughput
 // comes from the batch (1024 instances = 1024 wavefronts).
+//
+// The small helpers this file has in common with the loop kernel and waa_frozen.hip — the param read through load_global, the
+// agent-scope coherent loads, the curve lookup in global memory, M2d / mm2, lds_sync — are waa_quantum.hpp.  dyn_lds_layout
+// below is the one definition of the kernel's dynamic LDS: dyn_lds_bytes takes its total, static_asserts pin it, and dyn_body
+// walks its fields in order.  dyn_body itself is still one scope: a cut into phases that shared the Biquad scan and the
+// DelayReader arithmetic with loop_kernel rendered bit-identically but moved registers, scalar spills and the time of one
+// two-stage graph (profiles/quantum_kernels_resource_diff.txt), so it is not in the tree.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,33 +26,11 @@
 
 #include "waa_internal.hpp"
 #include "waa_mix.hpp"
+#include "waa_quantum.hpp"
 
 namespace waa {
 
 namespace {
-__device__ __forceinline__ float pval(const ParamRef& p, uint32_t inst, uint32_t q, uint64_t frame) {
-  if (p.mode == 0) return load_global(p.base + inst);
-  if (p.mode == 1) return load_global(p.base + (uint64_t)inst * p.stride + q);
-  return load_global(p.base + (uint64_t)inst * p.stride + frame);
-}
-__device__ __forceinline__ float coherent_f(const float* p) {
-  return __int_as_float(__hip_atomic_load((const WAA_GLOBAL_AS int*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ uint32_t coherent_u(const uint32_t* p) {
-  return (uint32_t)__hip_atomic_load((const WAA_GLOBAL_AS int*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// waveshaper.rs:555-573
-__device__ __forceinline__ float shape(const float* curve, int nn, float input) {
-  if (nn == 0) return 0.f;
-  const float n = (float)nn;
-  const float v = (n - 1.f) / 2.0f * (input + 1.f);
-  if (v <= 0.f) return load_global(curve);
-  if (v >= n - 1.f) return load_global(curve + nn - 1);
-  const float k = floorf(v);
-  const float f = v - k;
-  const int ki = (int)k;
-  return (1.f - f) * load_global(curve + ki) + f * load_global(curve + ki + 1);
-}
 // quantum.rs:285-505 mix_inner; `sil` = every channel is the allocator's zero block.  A computed down-mix goes through
 // make_mut, so its result is no longer silent by pointer identity (quantum.rs:96-104); up-mixes copy or pad.
 template <int CM>
@@ -54,17 +39,6 @@ __device__ __forceinline__ void mixn(float (&u)[CM][2], int from, int to, int in
   mix_regs<CM, 2>(u, from, to, interp);
   if (mix_is_computed(from, to, interp)) sil = false;
 }
-struct M2d {
-  double a, b, c, d;
-};
-__device__ __forceinline__ M2d mm2(const M2d& x, const M2d& y) {
-  M2d r;
-  r.a = __builtin_fma(x.a, y.a, x.b * y.c);
-  r.b = __builtin_fma(x.a, y.b, x.b * y.d);
-  r.c = __builtin_fma(x.c, y.a, x.d * y.c);
-  r.d = __builtin_fma(x.c, y.b, x.d * y.d);
-  return r;
-}
 __device__ __forceinline__ void stereo_gains(float x, float& gl, float& gr) {  // stereo_panner.rs:74-79
   const float PI_F = 3.14159265358979323846f;
   gl = sinf((1.f - x) * PI_F / 2.f);
@@ -72,16 +46,71 @@ __device__ __forceinline__ void stereo_gains(float x, float& gl, float& gr) {  /
 }
 }  // namespace
 
-// One workgroup = one wavefront: LDS hand-offs between lanes need program order only (the DS operations of a wave execute
-// in order).  __syncthreads() would also drain every outstanding global store (its release fence waits for vmcnt(0)) —
-// with four to five of them per filter item and quantum the wave waited for its own output stores a dozen times per quantum.
-__device__ __forceinline__ void lds_sync() { __builtin_amdgcn_wave_barrier(); }
-
 // CM = 2: mono / stereo graphs (the round-2 kernel); CM = 6: layouts up to 5.1 (DelayNodes stay mono / stereo: the planner checks)
 static_assert(offsetof(DynItem, kind) == 0 && offsetof(DynItem, cc) == 8 && offsetof(DynItem, interp) == 16 && offsetof(DynItem, nch_pub) == 24 &&
                   offsetof(DynItem, compact_ch1) == 32 && offsetof(DynItem, writer_item) == 40 && offsetof(DynItem, num_quanta) == 48 &&
                   offsetof(DynItem, in) == 56 && sizeof(DynItem) % 8 == 0,
               "dyn_kernel reads the item's scalar fields as seven 8-byte words");
+// ---- the dynamic LDS of dyn_kernel<CM, W>: byte offsets from its start.  dyn_lds_bytes (the planner's residency and stage
+// decisions) takes the total; dyn_body carves its pointers field by field in this order (as a chain of typed pointers: carved from
+// these byte offsets every instantiation compiles to other code, so the chain stays and the totals below pin the two together).
+struct DynLds {
+  size_t cur_ring;    // float [W][n_items][CM][128] outputs of the last W quanta
+  // (W > 1) the MIXED INPUTS of the last W quanta: an item's front half (gather + mix) and back half (node + hand-over) may
+  // belong to different stages
+  // (two slots: an item's gather and node are consecutive units, so their stages are the same or neighbours)
+  size_t mix_ring;    // float [2][n_items][CM][128] (W > 1 only)
+  size_t scratch;     // float [W][CM][128]
+  size_t fst;         // double [n_items][CM][DYN_STATE] filter state
+  size_t ist;         // int [n_items][4] integer state
+  size_t codes_ring;  // int [W][n_items] codes of the last W quanta
+  size_t meta_ring;   // int [2][n_items] count | silent << 8 of the mixed inputs (W > 1 only)
+  // per-item caches of what never changes from quantum to quantum: the params with ONE value per instance (ParamRef mode 0: a global
+  // load per use, ~700 cycles each, three in a row in a panner item) and a Biquad's constant coefficient set (five doubles)
+  size_t pmask;       // int [n_items] bit s: slot s is cached; bit 8: the coefficients
+  size_t pcs;         // float [n_items][8]: op.p0 .. op.p4, alt1, alt2
+  size_t cfs;         // double [n_items][5], aligned to 8 bytes
+  size_t items;       // DynItem [n_items]
+  size_t total;
+};
+__host__ __device__ constexpr DynLds dyn_lds_layout(int n_items, int cm, int w) {
+  const size_t n = (size_t)n_items, mixd = w > 1 ? 2 : 0;
+  DynLds l{};
+  size_t o = 0;
+  l.cur_ring = o, o += (size_t)w * n * cm * RQ * sizeof(float);
+  l.mix_ring = o, o += mixd * n * cm * RQ * sizeof(float);
+  l.scratch = o, o += (size_t)w * cm * RQ * sizeof(float);
+  l.fst = o, o += n * cm * DYN_STATE * sizeof(double);
+  l.ist = o, o += n * 4 * sizeof(int);
+  l.codes_ring = o, o += (size_t)w * n * sizeof(int);
+  l.meta_ring = o, o += mixd * n * sizeof(int);
+  l.pmask = o, o += n * sizeof(int);
+  l.pcs = o, o += n * 8 * sizeof(float);
+  const size_t pad = (8 - o % 8) % 8;  // an odd number of 4-byte words in front of the doubles: one pad word
+  l.cfs = o + pad, o = l.cfs + n * 5 * sizeof(double);
+  l.items = o, o += n * sizeof(DynItem);
+  // (the total has always budgeted two words for the alignment step whatever it took; the planner's choices hang on the figure)
+  l.total = o - pad + 8;
+  return l;
+}
+// the totals of the closed formula this replaced, (n_items, cm, w) -> bytes: odd and even item counts, stereo / 5.1 / 32 channels,
+// one, two and five stages (a DynItem of another size moves them all: pin them again)
+#define DYN_LDS_PIN(n, cm, w, bytes) static_assert(dyn_lds_layout(n, cm, w).total == bytes, "dyn_kernel's LDS total moved: the planner decides by it")
+DYN_LDS_PIN(1, 2, 1, 3400);
+DYN_LDS_PIN(6, 2, 1, 15240);
+DYN_LDS_PIN(48, 2, 1, 114696);
+DYN_LDS_PIN(7, 2, 2, 40220);
+DYN_LDS_PIN(8, 2, 2, 45672);
+DYN_LDS_PIN(5, 2, 5, 47808);
+DYN_LDS_PIN(12, 2, 5, 107560);
+DYN_LDS_PIN(3, 6, 1, 18248);
+DYN_LDS_PIN(4, 6, 1, 23304);
+DYN_LDS_PIN(2, 32, 1, 61448);
+DYN_LDS_PIN(9, 32, 1, 219144);
+#undef DYN_LDS_PIN
+static_assert(dyn_lds_layout(7, 2, 2).cfs % 8 == 0 && dyn_lds_layout(8, 2, 2).cfs % 8 == 0 && dyn_lds_layout(7, 2, 2).items % 8 == 0,
+              "doubles and descriptors on 8-byte boundaries");
+
 // W = 1: one wavefront per instance walks items and quanta (the form of rounds 2-4).  W > 1 (round 5): the items — in THIRDS: the
 // gather + mix of an item's inputs, its node (result into LDS), the result's publication to memory — are cut into W
 // contiguous STAGES (DynDesc::stage_begin, the planner's choice: a DelayNode's writer and reader and everything between them
@@ -239,7 +268,7 @@ __device__ __forceinline__ void dyn_body(const DynDesc& d) {
       const int h_num_quanta = __builtin_amdgcn_readfirstlane(hw6.x);
       const int h_pmask = __builtin_amdgcn_readfirstlane(pmask_s[it]);
       auto pvc = [&](int slot, const ParamRef& p, uint64_t frame) __attribute__((always_inline)) {
-        return (h_pmask >> slot) & 1 ? pcs[it * 8 + slot] : pval(p, inst, q, frame);
+        return (h_pmask >> slot) & 1 ? pcs[it * 8 + slot] : param_val(p, inst, q, frame);
       };
       const bool do_front = W == 1 || (3 * it >= u0 && 3 * it < u1), do_node = W == 1 || (3 * it + 1 >= u0 && 3 * it + 1 < u1),
                  do_pub = W == 1 || (3 * it + 2 >= u0 && 3 * it + 2 < u1);  // (uniform; a stage's units are contiguous)
@@ -375,7 +404,7 @@ __device__ __forceinline__ void dyn_body(const DynDesc& d) {
               }
 #pragma unroll
               for (int e = 0; e < 2; e++) {
-                float g = m[e] + pval(op.p0, inst, q, f0 + e * 64 + lane);
+                float g = m[e] + param_val(op.p0, inst, q, f0 + e * 64 + lane);
                 g = g != g ? li.pmod_def : fminf(fmaxf(g, li.pmod_min), li.pmod_max);
 #pragma unroll
                 for (int c = 0; c < CM; c++) v[c][e] *= g;
@@ -643,7 +672,7 @@ __device__ __forceinline__ void dyn_body(const DynDesc& d) {
               for (int c = 0; c < CM; c++)
                 if (c < sn) {
 #pragma unroll
-                  for (int e = 0; e < 2; e++) v[c][e] = shape(curve, op.i0, v[c][e]);
+                  for (int e = 0; e < 2; e++) v[c][e] = shape_curve(curve, op.i0, v[c][e]);
                 }
               outs = false;
             }
@@ -793,7 +822,7 @@ __device__ __forceinline__ void dyn_body(const DynDesc& d) {
         int64_t pf0 = 0;
         float k0 = 0.f;
         if (op.p0.mode != 2) {
-          double dv = (double)pval(op.p0, inst, q, 0);
+          double dv = (double)param_val(op.p0, inst, q, 0);
           if (h_in_cycle) dv = fmax(dv, d.quantum_duration);
           const double position = 0. - dv * d.sample_rate;
           const double fl = floor(position);
@@ -994,13 +1023,7 @@ void launch_dyn(const DynDesc& d, void* stream) {
 size_t dyn_lds_bytes(int n_items, int cmax, int stages) {
   const int cm = dyn_planes(cmax);
   const int w = cm == 2 && stages > 1 ? stages : 1;
-  // signals (a ring of w quanta; w > 1: a second ring, the mixed inputs) + scratch (per stage), filter state, ist (4) + codes (w)
-  // (+ meta (w)) + pmask (1) ints (+ the pad word in front of the doubles), the param cache (8 floats), the coefficient cache
-  // (5 doubles), the item descriptors
-  const size_t mixd = w > 1 ? 2 : 0;  // (the mixed inputs: two slots, neighbours hand over)
-  return (((size_t)w + mixd) * n_items * cm * RQ + (size_t)w * cm * RQ) * sizeof(float) + (size_t)n_items * cm * DYN_STATE * sizeof(double) +
-         (size_t)(n_items * (5 + w + mixd) + 2) * sizeof(int) + (size_t)n_items * 8 * sizeof(float) + (size_t)n_items * 5 * sizeof(double) +
-         (size_t)n_items * sizeof(DynItem);
+  return dyn_lds_layout(n_items, cm, w).total;
 }
 
 // ConvolverRenderer::process on codes (convolver.rs:343-392): the tail counter cuts the output off once a silent input

@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "waa_internal.hpp"
+#include "waa_quantum.hpp"
 
 namespace waa {
 
@@ -197,17 +198,7 @@ namespace {
 constexpr int BM = 128, BN = 128, BK = 16;
 constexpr int LDA = BM + 4, LDB = BN + 4;  // padded LDS rows (bank spread of the transposing stores)
 
-__device__ __forceinline__ float shape_curve(const float* curve, int nn, float input) {  // waveshaper.rs:555-573
-  if (nn == 0) return 0.f;
-  const float n = (float)nn;
-  const float v = (n - 1.f) / 2.0f * (input + 1.f);
-  if (v <= 0.f) return load_global(curve);
-  if (v >= n - 1.f) return load_global(curve + nn - 1);
-  const float k = floorf(v);
-  const float f = v - k;
-  const int ki = (int)k;
-  return (1.f - f) * load_global(curve + ki) + f * load_global(curve + ki + 1);
-}
+// (shape_curve, the lookup on a curve in global memory: waa_quantum.hpp)
 constexpr int CURVE_LDS = 4100;
 __device__ __forceinline__ float shape_curve_lds(const float* curve, int nn, float input) {  // waveshaper.rs:555-573
   if (nn == 0) return 0.f;
