@@ -61,9 +61,10 @@ def g_c5(be):
     return ctx
 
 
-def _echo_loop(be, delay_time, shaper=False):
-    """source -> Delay <-> [WaveShaper ->] Gain, the delay into the destination"""
-    c = _ctx(be)
+def _echo_loop(be, delay_time, shaper=False, **kw):
+    """source -> Delay <-> [WaveShaper ->] Gain, the delay into the destination (kw: n / frames / device of the batch, as for every
+    builder below that takes it — tests/test_batch_sizes.py renders them at other batch sizes)"""
+    c = _ctx(be, **kw)
     s = _source(c)
     d = c.create_delay(1.0, delay_time=delay_time)
     s.connect(d)
@@ -73,8 +74,8 @@ def _echo_loop(be, delay_time, shaper=False):
     return c
 
 
-def g_echo_ring(be):            # block-scheduled (2400 frames > a tile), one launch of the LDS-ring kernel
-    return _echo_loop(be, 0.05)
+def g_echo_ring(be, **kw):      # block-scheduled (2400 frames > a tile), one launch of the LDS-ring kernel
+    return _echo_loop(be, 0.05, **kw)
 
 
 def g_echo_ring_tail(be):       # ... whose line has one reader, dry + wet: the fused tail
@@ -88,8 +89,8 @@ def g_echo_ring_tail(be):       # ... whose line has one reader, dry + wet: the 
     return c
 
 
-def g_loop_kernel(be):          # 132 frames: below the ring kernel's smallest chunk
-    return _echo_loop(be, 0.00275)
+def g_loop_kernel(be, **kw):    # 132 frames: below the ring kernel's smallest chunk
+    return _echo_loop(be, 0.00275, **kw)
 
 
 def g_loop_kernel_shaper(be):   # 480 frames around a WaveShaper: planned for the ring, does not qualify, planned again
@@ -155,19 +156,19 @@ def g_feed_forward_echo(be):    # 256 contexts: one per CU, the ring kernel with
     return c
 
 
-def g_delay_gather(be):         # a delay in front of a convolver keeps the gather kernel
-    c = _ctx(be)
+def g_delay_gather(be, **kw):   # a delay in front of a convolver keeps the gather kernel
+    c = _ctx(be, **kw)
     s = _source(c)
     d = c.create_delay(1.0, delay_time=0.05)
     s.connect(d).connect(c.create_convolver(buffer=waa.AudioBuffer(np.ones((1, 300), np.float32), SR))).connect(c.destination())
     return c
 
 
-def _frozen_loop(be, kind, delay_time):
+def _frozen_loop(be, kind, delay_time, **kw):
     """a burst -> Delay -> oversampled WaveShaper / HRTF panner -> Gain -> back (tests/test_frozen_loops.py): dynamic counts, the
     loop cut at the node and launched quantum block by quantum block"""
-    n, frames = 3, RQ * 70 + 33
-    c = _ctx(be, n=n, frames=frames)
+    c = _ctx(be, **{"frames": RQ * 70 + 33, **kw})
+    n = c.n_instances
     s = c.create_buffer_source()
     s.set_buffer_batch(white_noise(n, 2, RQ * 20 + 7, seed0=5) * np.float32(0.6), SR)
     d = c.create_delay(0.1, delay_time=delay_time)
@@ -177,16 +178,16 @@ def _frozen_loop(be, kind, delay_time):
     d.connect(f).connect(c.create_gain(gain=0.45)).connect(d)
     f.connect(c.destination())
     for i in range(n):
-        s.start_at(i * 211.0 / SR, instance=i)
+        s.start_at((i % 14) * 211.0 / SR, instance=i)
     return c
 
 
-def g_qloop_shaper_2x(be):
-    return _frozen_loop(be, "2x", 0.01)
+def g_qloop_shaper_2x(be, **kw):
+    return _frozen_loop(be, "2x", 0.01, **kw)
 
 
-def g_qloop_hrtf(be):
-    return _frozen_loop(be, "hrtf", 0.01)
+def g_qloop_hrtf(be, **kw):
+    return _frozen_loop(be, "hrtf", 0.01, **kw)
 
 
 def g_qloop_automated(be):
@@ -210,9 +211,8 @@ def g_qloop_automated(be):
     return c
 
 
-def g_qloop_conv_and_shaper(be):
-    n, frames = 3, RQ * 70 + 33
-    c = _ctx(be, n=n, frames=frames)
+def g_qloop_conv_and_shaper(be, **kw):
+    c = _ctx(be, **{"frames": RQ * 70 + 33, **kw})
     s = _source(c, frames=RQ * 30, seed0=33, scale=0.4)
     d = c.create_delay(0.1, delay_time=0.005)
     cv = c.create_convolver(buffer=waa.AudioBuffer(_decaying_ir(2, 300, 7), SR))
@@ -234,14 +234,14 @@ def g_qloop_long_conv_refused(be):  # partitions that span several quanta in a s
     return c
 
 
-def g_oversampled_shaper(be):   # outside any loop, static counts: the transform form in one launch (under WAA_OS_MATRIX: two qgemm stages)
-    c = _ctx(be, frames=RQ * 40)
+def g_oversampled_shaper(be, **kw):  # outside any loop, static counts: the transform form in one launch (under WAA_OS_MATRIX: two qgemm stages)
+    c = _ctx(be, **{"frames": RQ * 40, **kw})
     _source(c).connect(c.create_wave_shaper(curve=CURVE, oversample="4x")).connect(c.destination())
     return c
 
 
-def g_listener_automated_in_a_loop(be):  # ... the panner inside a block-scheduled loop: the geometry runs once in front of the blocks
-    c = _ctx(be)
+def g_listener_automated_in_a_loop(be, **kw):  # ... the panner inside a block-scheduled loop: the geometry runs once in front of the blocks
+    c = _ctx(be, **kw)
     c.listener().position_x.set_value_at_time(0.0, 0.0).linear_ramp_to_value_at_time(1.0, 0.3)
     s = _source(c)
     d = c.create_delay(1.0, delay_time=0.05)
@@ -263,17 +263,17 @@ def g_biquad_a_rate_shared(be):  # one shared coefficient table: coefs, hp diges
     return ctx
 
 
-def g_iir(be):
-    c = _ctx(be, frames=RQ * 64)
+def g_iir(be, **kw):
+    c = _ctx(be, **{"frames": RQ * 64, **kw})
     _source(c).connect(c.create_iir_filter([0.2, 0.3, 0.1], [1.0, -0.5, 0.2])).connect(c.destination())
     return c
 
 
-def g_fm_pair(be):
-    c = _ctx(be, n=3, frames=RQ * 40)
+def g_fm_pair(be, **kw):
+    c = _ctx(be, **{"frames": RQ * 40, **kw})
     mod, idx, car = c.create_oscillator(type_="sine", frequency=110.0), c.create_gain(gain=300.0), c.create_oscillator(type_="sine", frequency=440.0)
-    for i in range(3):
-        car.detune.set_value(25.0 * i, instance=i)
+    for i in range(c.n_instances):
+        car.detune.set_value(25.0 * (i % 14), instance=i)
     mod.connect(idx).connect(car.frequency)
     car.connect(c.destination())
     mod.start()
@@ -281,8 +281,8 @@ def g_fm_pair(be):
     return c
 
 
-def g_compressor(be):
-    c = _ctx(be, n=2, frames=RQ * 64)
+def g_compressor(be, **kw):
+    c = _ctx(be, **{"n": 2, "frames": RQ * 64, **kw})
     _source(c).connect(c.create_dynamics_compressor()).connect(c.destination())
     return c
 
@@ -300,8 +300,8 @@ def g_compressor_behind_an_echo_loop(be):  # a kind the echo-tail fusion does no
     return c
 
 
-def g_splitter_merger(be):      # swap the channels: splitter -> merger
-    c = _ctx(be, frames=RQ * 30)
+def g_splitter_merger(be, **kw):  # swap the channels: splitter -> merger
+    c = _ctx(be, **{"frames": RQ * 30, **kw})
     s = _source(c)
     sp, mg = c.create_channel_splitter(2), c.create_channel_merger(2)
     s.connect(sp)
@@ -324,25 +324,24 @@ def g_merger_behind_an_echo_loop(be):
     return c
 
 
-def _per_instance_conv(be, taps):
-    n, frames = 3, RQ * 40
-    c = _ctx(be, n=n, frames=frames)
+def _per_instance_conv(be, taps, **kw):
+    c = _ctx(be, **{"frames": RQ * 40, **kw})
     conv = c.create_convolver()
-    conv.set_buffer_batch(np.stack([_decaying_ir(2, taps, 100 + 7 * i) for i in range(n)]), SR)
+    conv.set_buffer_batch(np.stack([_decaying_ir(2, taps, 100 + 7 * (i % 14)) for i in range(c.n_instances)]), SR)
     _source(c).connect(conv).connect(c.destination())
     return c
 
 
-def g_per_instance_conv_direct(be):
-    return _per_instance_conv(be, 100)
+def g_per_instance_conv_direct(be, **kw):
+    return _per_instance_conv(be, 100, **kw)
 
 
-def g_per_instance_conv_fft(be):
-    return _per_instance_conv(be, 1500)
+def g_per_instance_conv_fft(be, **kw):
+    return _per_instance_conv(be, 1500, **kw)
 
 
-def g_block_loop_zero_conv(be):  # the fill inside a block-scheduled loop: once in front of the blocks
-    c = _ctx(be, frames=2048 * 6)
+def g_block_loop_zero_conv(be, **kw):  # the fill inside a block-scheduled loop: once in front of the blocks
+    c = _ctx(be, **{"frames": 2048 * 6, **kw})
     s = _source(c)
     d = c.create_delay(0.1, delay_time=0.06)
     cv = c.create_convolver(buffer=waa.AudioBuffer(np.zeros((2, 64), np.float32), SR))
@@ -360,13 +359,14 @@ def g_misordered_refused(be):   # (with WAA_DEBUG_REVERSE_PLAN: the validator's 
     return c
 
 
-def g_timeline(be, device=waa.PLAN_ONLY):
+def g_timeline(be, device=waa.PLAN_ONLY, **kw):
     """a gain with another automation per context: replayed on the device where there is one (StepKind::Timeline), evaluated on
     the host by a plan-only batch"""
-    c = _ctx(be, frames=RQ * 40, device=device)
+    c = _ctx(be, **{"frames": RQ * 40, **kw}, device=device)
     g = c.create_gain(gain=0.5)
-    for i in range(3):
-        g.gain.set_value_at_time(0.1 * (i + 1), 0.0, instance=i).linear_ramp_to_value_at_time(1.0, 0.05 + 0.01 * i, instance=i)
+    for i in range(c.n_instances):
+        k = i % 14
+        g.gain.set_value_at_time(0.1 * (k + 1), 0.0, instance=i).linear_ramp_to_value_at_time(1.0, 0.05 + 0.01 * k, instance=i)
     _source(c).connect(g).connect(c.destination())
     return c
 

@@ -218,7 +218,24 @@ __global__ __launch_bounds__(256) void compressor_apply_kernel(const CompDesc d)
   }
 }
 
+// level and apply have the instance on gridDim.y: a batch of more instances than a grid has rows goes in slices
+template <class L>
+static bool comp_sliced(const CompDesc& d, L&& launch) {
+  if (d.n_inst <= MAX_GRID_ROWS) return false;
+  for_grid_row_slices(d.n_inst, 1, [&](uint32_t first, uint32_t count) {
+    CompDesc s = d;
+    advance_instances(s.in, first);
+    advance_instances(s.out, first);
+    advance_instances(s.xl, first, d.frames);
+    advance_instances(s.rows, first, d.row_inst_stride);
+    s.n_inst = count;
+    launch(s);
+  });
+  return true;
+}
+
 void launch_compressor_level(const CompDesc& d, void* stream) {
+  if (comp_sliced(d, [&](const CompDesc& s) { launch_compressor_level(s, stream); })) return;
   const dim3 grid((uint32_t)(((uint64_t)d.n_quanta * RQ + 1023) / 1024), d.n_inst), block(256);
   hipLaunchKernelGGL(compressor_level_kernel, grid, block, 0, (hipStream_t)stream, d);
 }
@@ -232,6 +249,7 @@ void launch_compressor_detector(const CompDesc& d, void* stream) {
 }
 
 void launch_compressor_apply(const CompDesc& d, void* stream) {
+  if (comp_sliced(d, [&](const CompDesc& s) { launch_compressor_apply(s, stream); })) return;
   const dim3 grid((uint32_t)((d.frames + 1023) / 1024), d.n_inst), block(256);
   hipLaunchKernelGGL(compressor_apply_kernel, grid, block, 0, (hipStream_t)stream, d);
 }

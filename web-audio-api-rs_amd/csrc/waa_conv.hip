@@ -865,7 +865,32 @@ static void allow_big_lds(size_t bytes) {
   raise_lds_limit(reinterpret_cast<const void*>(conv_fft_pipe_kernel<MODE_INV, 2>));
 }
 
+// ---- batches of more instance pairs (gridDim.z; gridDim.y / cout in the products) or instances (direct form, per-instance
+// ---- spectra) than a grid has rows: the launchers below, and those of waa_conv3.hip and waa_conv_inst.hip, launch slices
+ConvDesc conv_instance_slice(const ConvDesc& d, uint32_t inst0, uint32_t n_inst) {
+  ConvDesc s = d;
+  advance_instances(s.in, inst0);
+  advance_instances(s.out, inst0);
+  advance_instances(s.pre_coefs, inst0, d.pre_coef_stride);
+  advance_instances(s.pre_state, inst0, STATE_STRIDE);
+  if (d.per_inst) {
+    advance_instances(s.ir, inst0, d.ir_inst_stride);
+    advance_instances(s.H, inst0, (uint64_t)d.ir_nch * d.parts * d.n);
+  }
+  s.n_inst = n_inst;
+  s.n_pairs = (n_inst + 1) / 2;
+  return s;
+}
+ConvDesc conv_pair_slice(const ConvDesc& d, uint32_t pair0, uint32_t n_pairs) {
+  const uint32_t inst0 = pair0 * 2, left = d.n_inst - inst0;  // (an odd batch's single instance stays the last slice's last)
+  ConvDesc s = conv_instance_slice(d, inst0, left < n_pairs * 2 ? left : n_pairs * 2);
+  advance_instances(s.X, pair0, (uint64_t)d.cin * d.nb * d.n);
+  advance_instances(s.Y, pair0, (uint64_t)d.cout * d.nb * d.n);
+  return s;
+}
+
 void launch_conv_ir_spectra(const ConvDesc& d, void* stream) {
+  if (d.per_inst && conv_instances_sliced(d, [&](const ConvDesc& s) { launch_conv_ir_spectra(s, stream); })) return;
   if (d.fft3) return launch_conv3_ir_spectra(d, stream);
   allow_big_lds((size_t)d.n * sizeof(Cplx));
   hipLaunchKernelGGL(conv_fft_kernel<MODE_IR>, dim3(d.parts, d.ir_nch, d.per_inst ? d.n_inst : 1), dim3(fft_threads(d.n)),
@@ -882,6 +907,7 @@ static int pipe_blocks_per_wg(const ConvDesc& d, int channels) {
 static bool use_pipe(const ConvDesc& d) { return d.n == PIPE_N && !measure_switch("WAA_CONV_FFT_PLAIN"); }
 
 void launch_conv_forward(const ConvDesc& d, void* stream) {
+  if (conv_pairs_sliced(d, 1, [&](const ConvDesc& s) { launch_conv_forward(s, stream); })) return;
   if (d.fft3) return launch_conv3_forward(d, stream);
   allow_big_lds((size_t)d.n * sizeof(Cplx));
   if (use_pipe(d)) {
@@ -901,6 +927,7 @@ void launch_conv_forward(const ConvDesc& d, void* stream) {
                      (hipStream_t)stream, d);
 }
 void launch_conv_inverse(const ConvDesc& d, void* stream) {
+  if (conv_pairs_sliced(d, 1, [&](const ConvDesc& s) { launch_conv_inverse(s, stream); })) return;
   if (d.fft3) return launch_conv3_inverse(d, stream);
   allow_big_lds((size_t)d.n * sizeof(Cplx));
   if (use_pipe(d)) {
@@ -920,6 +947,7 @@ void launch_conv_inverse(const ConvDesc& d, void* stream) {
                      (hipStream_t)stream, d);
 }
 void launch_conv_direct(const ConvDesc& d, void* stream) {
+  if (conv_instances_sliced(d, [&](const ConvDesc& s) { launch_conv_direct(s, stream); })) return;
   dim3 grid((unsigned)(d.kb1 - d.kb0), d.cout, d.n_inst);
   hipLaunchKernelGGL(conv_direct_kernel, grid, dim3(256), 0, (hipStream_t)stream, d);
 }
@@ -929,6 +957,7 @@ void launch_analyser(const AnalyserDesc& d, void* stream) {
   hipLaunchKernelGGL(analyser_kernel, dim3(d.n_inst), dim3(fft_threads(M)), (size_t)M * sizeof(Cplx), (hipStream_t)stream, d);
 }
 void launch_conv_mac(const ConvDesc& d0, void* stream) {
+  if (conv_pairs_sliced(d0, (uint32_t)d0.cout, [&](const ConvDesc& s) { launch_conv_mac(s, stream); })) return;
   dim3 grid(d0.n / 256, d0.n_pairs * (uint32_t)d0.cout);
   ConvDesc dm = d0;
   dm.mac_grid_order = measure_switch("WAA_CONV_MAC_GRID_ORDER") ? 1 : 0;

@@ -238,11 +238,13 @@ __global__ __launch_bounds__(256) void conv_inst_direct_kernel(const ConvDesc d)
 }  // namespace
 
 void launch_conv_inst_direct(const ConvDesc& d, void* stream) {
+  if (conv_instances_sliced(d, [&](const ConvDesc& s) { launch_conv_inst_direct(s, stream); })) return;  // (gridDim.z)
   dim3 grid((unsigned)(d.kb1 - d.kb0), d.cout, d.n_inst);
   hipLaunchKernelGGL(conv_inst_direct_kernel, grid, dim3(256), 0, (hipStream_t)stream, d);
 }
 
 void launch_conv_inst_mac(const ConvDesc& d, void* stream) {
+  if (conv_pairs_sliced(d, (uint32_t)d.cout, [&](const ConvDesc& s) { launch_conv_inst_mac(s, stream); })) return;  // (gridDim.y)
   dim3 grid(d.n / 256, d.n_pairs * (uint32_t)d.cout);
   const int log2n = 31 - __builtin_clz((unsigned)d.n);
   bool one_term = true;

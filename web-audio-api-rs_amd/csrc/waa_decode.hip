@@ -10,8 +10,6 @@
 
 namespace waa {
 
-constexpr uint32_t MAX_GRID_ROWS = 65535;  // gridDim.y limit
-
 __device__ __forceinline__ void pcm16_resample_item(const DecodeDesc& d, uint32_t item, uint64_t i);
 __global__ __launch_bounds__(256) void pcm16_resample_kernel(const DecodeDesc d) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;

@@ -54,6 +54,17 @@ __global__ __launch_bounds__(256) void delay_kernel(const DelayDesc d) {
 }
 
 void launch_delay(const DelayDesc& d, void* stream) {
+  if ((uint64_t)d.n_inst * (uint32_t)d.nch > MAX_GRID_ROWS) {  // more rows than a grid has: slices of whole instances
+    for_grid_row_slices(d.n_inst, (uint32_t)d.nch, [&](uint32_t first, uint32_t count) {
+      DelayDesc s = d;
+      advance_instances(s.in, first);
+      advance_instances(s.out, first);
+      advance_instances(s.delay, first);
+      s.n_inst = count;
+      launch_delay(s, stream);
+    });
+    return;
+  }
   const dim3 grid((uint32_t)(((uint64_t)(d.tile1 - d.tile0) * TILE + 1023) / 1024), d.n_inst * (uint32_t)d.nch), block(256);
   hipLaunchKernelGGL(delay_kernel, grid, block, 0, (hipStream_t)stream, d);
 }

@@ -1094,9 +1094,26 @@ void launch_hrtf(const HrtfDesc& d0, void* stream) {
   const uint32_t nq_launch = d.q1 - d.q0;
   // one direction for the whole batch: the FIR as partitioned overlap-add on 256-point transforms (waa_hrtf_fft.hip) — unless the
   // launch is a short range of a loop rendered block by block (a run pays four unstored quanta up front)
-  if (d.fft_tables && d.per_row == 1 && nq_launch >= 16 && !measure_switch("WAA_HRTF_DIRECT") && !measure_switch("WAA_HRTF_V1") &&
+  if (d.fft_tables && d.per_row == 1 && nq_launch >= HRTF_FFT_MIN_QUANTA && !measure_switch("WAA_HRTF_DIRECT") && !measure_switch("WAA_HRTF_V1") &&
       !measure_switch("WAA_HRTF_V8") && !measure_switch("WAA_HRTF_DYNAMIC")) {
     launch_hrtf_fft(d, stream);
+    return;
+  }
+  if (d.n_inst > MAX_GRID_ROWS) {  // the direct forms below have the instance on gridDim.y: a bigger batch goes in slices
+    for_grid_row_slices(d.n_inst, 1, [&](uint32_t first, uint32_t count) {
+      HrtfDesc s = d;
+      advance_instances(s.in, first);
+      advance_instances(s.out, first);
+      advance_instances(s.in_code, first, d.code_stride);
+      advance_instances(s.prev, first, d.prev_stride);
+      if (d.rows != 1) {  // (one row per instance: the geometry, the host-interpolated HRIR pair [O][2])
+        advance_instances(s.table, first, d.per_row);
+        advance_instances(s.hstatic, first, (uint64_t)2 * ((d.taps + 3) & ~3));
+      }
+      s.fft_tables = nullptr;  // (the transform form was not chosen above; its tables are per row as well)
+      s.n_inst = count;
+      launch_hrtf(s, stream);
+    });
     return;
   }
   if (!measure_switch("WAA_HRTF_V1")) {

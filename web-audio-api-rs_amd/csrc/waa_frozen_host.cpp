@@ -288,6 +288,10 @@ int plan_oversampler(waa_batch* b, uint32_t id, int src_id) {
               id, R, 2 + 2 * R, seg_len, n_seg, nch, can_propagate ? ", silent input skips the block" : "");
     return 0;
   }
+  // (a measured alternative only: it is not sliced like the product's launches, waa_internal.hpp MAX_GRID_ROWS)
+  if ((uint64_t)b->n_inst * nch > MAX_GRID_ROWS)
+    return fail(WAA_ERR_OUT_OF_SCOPE, "waveshaper node %u: launch_qgemm (WAA_OS_MATRIX) has one grid row per (context, channel), %llu here, and a grid has at most %u",
+                id, (unsigned long long)b->n_inst * nch, MAX_GRID_ROWS);
   float *d_up = nullptr, *d_dn = nullptr, *sbuf = nullptr;
   uint16_t *d_up16 = nullptr, *d_dn16 = nullptr;
   const std::vector<float> m_up = resampler_matrix(RQ, up_len), m_dn = resampler_matrix(up_len, RQ);
@@ -685,10 +689,11 @@ int plan_hrtf(waa_batch* b, uint32_t id, int src_id) {
   b->steps.push_back(st);
   if (fft_form)
     plan_note(b, "panner node %u: HRTF, %d-tap impulse responses at %u Hz, %s: %d partitions of 128 taps as 256-point "
-                 "transforms (2 per quantum, runs of %u quanta, %u per instance)", id, sp->taps, sp->sr,
+                 "transforms (2 per quantum, runs of %u quanta, %u per instance)%s", id, sp->taps, sp->sr,
               rows == 1 ? (d.jmax ? "one direction for the whole batch (exact zeros behind the response's reach)" : "one direction for the whole batch")
                         : (d.jmax ? "one direction per context (exact zeros behind the response's reach)" : "one direction per context"),
-              hrtffft::PARTS, d.seg_len, d.n_seg);
+              hrtffft::PARTS, d.seg_len, d.n_seg,
+              b->n_quanta < HRTF_FFT_MIN_QUANTA ? "; a launch of fewer than 16 quanta takes the direct form with the host-interpolated pair (hrtf8_kernel): this render does" : "");
   else
     plan_note(b, "panner node %u: HRTF, %d-tap impulse responses at %u Hz, geometry table %u row(s) x %u, direct FIR per render quantum", id,
               sp->taps, sp->sr, rows, per_row);

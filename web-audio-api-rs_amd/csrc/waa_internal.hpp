@@ -825,6 +825,7 @@ struct HrtfQ {              // host-evaluated geometry of one (instance, quantum
   int32_t pad;
 };
 constexpr int HRTF_MAX_TAPS = 1280;
+constexpr uint32_t HRTF_FFT_MIN_QUANTA = 16;  // launch_hrtf: shorter launches take the direct form (a run of the transform form pays four unstored quanta up front)
 struct HrtfDesc {
   SignalRef in, out;        // in: the node's mixed input (1 or 2 channels); out: 2 channels
   const uint8_t* in_code;   // [n_inst][code_stride]
@@ -915,6 +916,46 @@ void launch_quantum_heads(const float* src, uint64_t inst_stride, uint32_t n_ins
 // waa_resample.hip: AudioBufferSource [-> WaveShaper] -> signal without the op interpreter (the C5 shape)
 bool resample_shape(const ChainDesc& d, int* curve_op);
 void launch_resample(const ChainDesc& d, int curve_op, void* stream);
+
+// ---- launches that carry the batch on gridDim.y / gridDim.z ------------------------------------------------------------
+// A grid has at most 65535 rows in y and in z.  A launcher whose row count grows with the batch launches a bigger batch in
+// SLICES of whole instances (or instance pairs), one after the other on the same stream: every slice gets a copy of the
+// descriptor whose per-instance pointers are moved on to the slice's first instance, so the kernels — and the grid of every
+// batch within the limit — stay what they are.  (The PCM kernels of waa_decode.hip walk the rows in strides instead.)
+constexpr uint32_t MAX_GRID_ROWS = 65535;
+inline void advance_instances(SignalRef& s, uint64_t inst0) {
+  if (s.base) s.base += inst0 * s.inst_stride;
+}
+inline void advance_instances(ParamRef& p, uint64_t inst0) {
+  if (p.base) p.base += p.mode == 0 ? inst0 : inst0 * p.stride;
+}
+template <class T>
+inline void advance_instances(T*& p, uint64_t inst0, uint64_t stride = 1) {
+  if (p) p += inst0 * stride;
+}
+// launch(first, count) for consecutive runs of at most MAX_GRID_ROWS / rows_per_item items
+template <class L>
+inline void for_grid_row_slices(uint32_t n_items, uint32_t rows_per_item, L&& launch) {
+  const uint32_t step = MAX_GRID_ROWS / (rows_per_item ? rows_per_item : 1u);
+  for (uint32_t first = 0; first < n_items; first += step) launch(first, n_items - first < step ? n_items - first : step);
+}
+// instance pairs [pair0, pair0 + n_pairs) of a convolver's transforms and products, instances [inst0, inst0 + n_inst) of its
+// direct form and of the spectra of per-instance responses
+ConvDesc conv_pair_slice(const ConvDesc& d, uint32_t pair0, uint32_t n_pairs);
+ConvDesc conv_instance_slice(const ConvDesc& d, uint32_t inst0, uint32_t n_inst);
+// false: the pairs fit one grid (rows_per_pair rows each), nothing launched; true: launch(slice) ran for every slice
+template <class L>
+inline bool conv_pairs_sliced(const ConvDesc& d, uint32_t rows_per_pair, L&& launch) {
+  if ((uint64_t)d.n_pairs * rows_per_pair <= MAX_GRID_ROWS) return false;
+  for_grid_row_slices(d.n_pairs, rows_per_pair, [&](uint32_t first, uint32_t count) { launch(conv_pair_slice(d, first, count)); });
+  return true;
+}
+template <class L>
+inline bool conv_instances_sliced(const ConvDesc& d, L&& launch) {
+  if (d.n_inst <= MAX_GRID_ROWS) return false;
+  for_grid_row_slices(d.n_inst, 1, [&](uint32_t first, uint32_t count) { launch(conv_instance_slice(d, first, count)); });
+  return true;
+}
 
 #ifdef __HIPCC__
 // A pointer LOADED from memory (the per-instance source records) is a generic pointer to the compiler: every access

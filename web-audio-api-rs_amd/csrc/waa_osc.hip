@@ -105,6 +105,22 @@ __global__ __launch_bounds__(64) void osc_scan_kernel(const OscDesc d) {
 }
 
 void launch_osc(const OscDesc& d, void* stream) {
+  if (d.table_q && d.n_inst > MAX_GRID_ROWS) {
+    // the time-parallel kernels (here and in waa_osc_types.hip) have the instance on gridDim.y: slices of a bigger batch, with
+    // everything THEY read per instance moved on (the other forms have it on gridDim.x)
+    for_grid_row_slices(d.n_inst, 1, [&](uint32_t first, uint32_t count) {
+      OscDesc s = d;
+      advance_instances(s.out, first);
+      advance_instances(s.wave_row, first);
+      advance_instances(s.tq_row, first);
+      advance_instances(s.type_inst, first);
+      for (int k = 0; k < 2; k++) advance_instances(s.post_gain[k].base, first);  // (one value per instance: osc_store)
+      advance_instances(s.pa_intrinsic, first);
+      s.n_inst = count;
+      launch_osc(s, stream);
+    });
+    return;
+  }
   if (d.type_inst || d.fm_type_inst) {  // one type per instance (waa_osc_types.hip)
     // pass 0 of the prefix-sum form computes no waveform of its own: only a folded modulator's types reach it
     if (d.active && !d.fm_type_inst) hipLaunchKernelGGL(osc_scan_kernel<0>, dim3(d.n_inst, OSC_SEGMENTS), dim3(64), 0, (hipStream_t)stream, d);
