@@ -131,6 +131,38 @@ waa_status waa_biquad_set_type_instance(waa_batch* batch, uint32_t node, uint32_
  * keeps the types, like everything but the audio. */
 waa_status waa_oscillator_set_type_instance(waa_batch* batch, uint32_t node, uint32_t instance, int32_t type);
 
+/* PannerNode::new(PannerOptions{distance_model, ref_distance, max_distance, rolloff_factor, cone_*}) of ONE context of the batch
+ * (src/node/panner.rs:146-166, the setters at :545-641): in the reference every context builds its own PannerNode with its own
+ * options.  Replaces one batch, one plan and one launch sequence per distinct option set: a spatial augmentation that places a
+ * thousand clips, each at its own position with its own distance law, rolloff and directivity cone.  The fifteen position,
+ * orientation and listener AudioParams were per instance already.
+ *
+ * A call carries a COMPLETE set (there is no all-zero-means-defaults shorthand here); a later call for the same instance
+ * replaces the earlier one.  distance_model: as waa_node_desc.i[1] of a PANNER node, anything else is "bad distance model"
+ * (WAA_ERR_INVALID_ARGUMENT).  The values are checked like waa_batch_create checks d[0..5], with the reference's messages:
+ * "RangeError - refDistance cannot be negative", "RangeError - maxDistance must be strictly positive", "RangeError - rolloffFactor
+ * cannot be negative" (WAA_ERR_INVALID_ARGUMENT) and "InvalidStateError - coneOuterGain must be in the range [0, 1]"
+ * (WAA_ERR_INVALID_STATE).  Refused with WAA_ERR_INVALID_ARGUMENT: a NULL `options`, a non-zero `reserved`, an instance
+ * >= n_instances and a node of another kind; refused once the batch is planned (InvalidStateError).  instance =
+ * WAA_ALL_INSTANCES replaces the node's shared set (i[1], d[0..5]) and leaves the sets given to single instances alone; an
+ * instance without a set of its own uses the shared one.  The panning model (i[0]) is not part of the set: it decides the plan's
+ * shape and stays one per node.
+ *
+ * A node whose instances all resolve to one set plans and renders exactly as a shared node of that set (the same launches, table
+ * rows and plan text).  Where the sets differ, the host geometry of a single-valued listener and the HRTF geometry table take
+ * every instance's gains from its own set (the HRTF table then has one row per instance), and the per-frame geometry of an
+ * audio-rate listener is written by panner_geom_inst_kernel — panner_geom_kernel with the set read from a table of one 40-byte
+ * row per instance — into one table row per instance, even under one listener automation shared by the batch (7 tables x 4 B
+ * per frame and instance).  No consumer kernel differs.  Called at a suspend point it applies to the whole
+ * render, like every payload.  waa_batch_rearm keeps the sets, like everything but the audio. */
+typedef struct waa_panner_options {
+  int32_t distance_model;            /* as waa_node_desc.i[1] of a PANNER node */
+  int32_t reserved;                  /* 0 */
+  double ref_distance, max_distance, rolloff_factor;
+  double cone_inner_angle, cone_outer_angle, cone_outer_gain;
+} waa_panner_options;
+waa_status waa_panner_set_options_instance(waa_batch* batch, uint32_t node, uint32_t instance, const waa_panner_options* options);
+
 #ifdef __cplusplus
 }
 #endif

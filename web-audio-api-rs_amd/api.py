@@ -209,7 +209,14 @@ ABI_DEVICE = {
     "waveshaper_set_curve_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP, C.c_uint32]),
     "biquad_set_type_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, C.c_int32]),
     "oscillator_set_type_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, C.c_int32]),
+    "panner_set_options_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _VP]),
 }
+
+
+class PannerOptions(C.Structure):  # waa_panner_options (include/waa_hip_device.h)
+    _fields_ = [("distance_model", C.c_int32), ("reserved", C.c_int32), ("ref_distance", C.c_double), ("max_distance", C.c_double),
+                ("rolloff_factor", C.c_double), ("cone_inner_angle", C.c_double), ("cone_outer_angle", C.c_double),
+                ("cone_outer_gain", C.c_double)]
 
 
 class Binding:
@@ -1123,6 +1130,73 @@ class PannerNode(AudioNode):
         self.orientation_z = AudioParam(self, 5, orientation[2])
         self.params = [self.position_x, self.position_y, self.position_z, self.orientation_x, self.orientation_y,
                        self.orientation_z]
+        self._inst_options = {}  # instance -> {field: value}: one option set per context (waa_panner_set_options_instance)
+
+    OPTION_FIELDS = ("distance_model", "ref_distance", "max_distance", "rolloff_factor", "cone_inner_angle", "cone_outer_angle",
+                     "cone_outer_gain")
+
+    @staticmethod
+    def _check_option_values(fields):
+        """the refusals of waa_panner_set_options_instance, which are the reference's (panner.rs:408-428, :545-641)"""
+        if "distance_model" in fields and fields["distance_model"] not in DISTANCE_MODEL:
+            raise WaaError(1, "bad distance model")
+        if "ref_distance" in fields and not fields["ref_distance"] >= 0.0:
+            raise WaaError(1, "RangeError - refDistance cannot be negative")
+        if "max_distance" in fields and not fields["max_distance"] > 0.0:
+            raise WaaError(1, "RangeError - maxDistance must be strictly positive")
+        if "rolloff_factor" in fields and not fields["rolloff_factor"] >= 0.0:
+            raise WaaError(1, "RangeError - rolloffFactor cannot be negative")
+        if "cone_outer_gain" in fields and not 0.0 <= fields["cone_outer_gain"] <= 1.0:
+            raise WaaError(3, "InvalidStateError - coneOuterGain must be in the range [0, 1]")
+
+    def set_options(self, instance: int = ALL, **fields):
+        """fields: any of the constructor's option names (OPTION_FIELDS); another name is a TypeError.  instance = ALL: the options of
+        every context without a value of its own — the plain attributes, as assigning them does (checked when the batch is created).
+        instance = i: context i's own values for the given fields (every context of the reference builds its own PannerNode from its
+        own PannerOptions, panner.rs:146-166); bad values, an unknown distance model, an instance out of range and a call after the
+        batch exists (InvalidStateError) are refused at once.  May be called any number of times; for one instance and one field the
+        last call wins.  The panning model is not an option of this kind: it stays one per node."""
+        for name in fields:
+            if name not in self.OPTION_FIELDS:
+                raise TypeError(f"set_options() got an unexpected option '{name}' (the options are {', '.join(self.OPTION_FIELDS)})")
+        if instance == ALL:
+            for name, v in fields.items():
+                setattr(self, name, v)
+            return self
+        self._check_option_values(fields)
+        if self.context._handle is not None:
+            raise WaaError(3, "InvalidStateError - the batch is frozen once rendering has started")
+        if not 0 <= int(instance) < self.context.n_instances:
+            raise WaaError(1, f"instance {instance} out of range")
+        self._inst_options.setdefault(int(instance), {}).update(fields)
+        return self
+
+    def set_options_batch(self, options):
+        """options: a sequence of n_instances dicts of option fields, one per context"""
+        n = self.context.n_instances
+        if len(options) != n:
+            raise WaaError(1, f"set_options_batch takes n_instances = {n} option sets, got {len(options)}")
+        for i, o in enumerate(options):
+            self.set_options(instance=i, **o)
+        return self
+
+    def options_of(self, instance: int) -> dict:
+        """the complete option set context `instance` renders with: the shared attributes overlaid with its own fields (resolved
+        now: the order of the set_options calls does not matter)"""
+        if not 0 <= int(instance) < self.context.n_instances:
+            raise WaaError(1, f"instance {instance} out of range")
+        o = {name: getattr(self, name) for name in self.OPTION_FIELDS}
+        o.update(self._inst_options.get(int(instance), {}))
+        return o
+
+    @property
+    def per_instance(self) -> bool:
+        return bool(self._inst_options)
+
+    def _options_differ(self) -> bool:
+        if not self._inst_options:
+            return False
+        return len({tuple(self.options_of(i).values()) for i in range(self.context.n_instances)}) > 1
 
     def set_position(self, x, y, z):
         self.position_x.set_value(x)
@@ -1135,13 +1209,26 @@ class PannerNode(AudioNode):
         self.orientation_z.set_value(z)
 
     def _fill_desc(self, d):
+        o = {name: getattr(self, name) for name in self.OPTION_FIELDS}
+        if self.per_instance and self.context._b.prefix != "waa_":
+            if self._options_differ():  # (refused before the batch exists)
+                raise WaaError(4, "one PannerNode option set per instance is a feature of the device library; this binding keeps one "
+                                  "set per batch (render it one context at a time)")
+            o = self.options_of(0)  # (equal sets everywhere: the shared option)
         d.i[0] = PANNING_MODEL[self.panning_model]
-        d.i[1] = DISTANCE_MODEL[self.distance_model]
-        d.d[0], d.d[1], d.d[2] = self.ref_distance, self.max_distance, self.rolloff_factor
-        d.d[3], d.d[4], d.d[5] = self.cone_inner_angle, self.cone_outer_angle, self.cone_outer_gain
+        d.i[1] = DISTANCE_MODEL[o["distance_model"]]
+        d.d[0], d.d[1], d.d[2] = o["ref_distance"], o["max_distance"], o["rolloff_factor"]
+        d.d[3], d.d[4], d.d[5] = o["cone_inner_angle"], o["cone_outer_angle"], o["cone_outer_gain"]
 
     def _apply(self, ctx):
         super()._apply(ctx)
+        if self.per_instance and ctx._b.prefix == "waa_":
+            b, h = ctx._b, ctx._handle
+            for i in sorted(self._inst_options):  # one complete set per instance that has fields of its own
+                o = self.options_of(i)
+                row = PannerOptions(DISTANCE_MODEL[o["distance_model"]], 0, o["ref_distance"], o["max_distance"], o["rolloff_factor"],
+                                    o["cone_inner_angle"], o["cone_outer_angle"], o["cone_outer_gain"])
+                b.check(b.panner_set_options_instance(h, self.id, i, C.byref(row)))
         for i, prm in enumerate(ctx.listener().params):  # the AudioListener's params, addressed through this panner
             prm._apply(ctx, node_id=self.id, pid=6 + i)
 

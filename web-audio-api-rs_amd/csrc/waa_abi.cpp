@@ -163,11 +163,7 @@ static int init_node(waa_batch* b, uint32_t i) {
         n.desc.d[3] = 360.;
         n.desc.d[4] = 360.;
       }
-      if (!(n.desc.d[0] >= 0.)) return fail(WAA_ERR_INVALID_ARGUMENT, "RangeError - refDistance cannot be negative");
-      if (!(n.desc.d[1] > 0.)) return fail(WAA_ERR_INVALID_ARGUMENT, "RangeError - maxDistance must be strictly positive");
-      if (!(n.desc.d[2] >= 0.)) return fail(WAA_ERR_INVALID_ARGUMENT, "RangeError - rolloffFactor cannot be negative");
-      if (!(n.desc.d[5] >= 0. && n.desc.d[5] <= 1.))
-        return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - coneOuterGain must be in the range [0, 1]");
+      if (int e = check_panner_values(n.desc.d[0], n.desc.d[1], n.desc.d[2], n.desc.d[5])) return e;
       break;
     }
     case WAA_NODE_DELAY:  // delay.rs:283-335

@@ -348,6 +348,38 @@ waa_status waa_biquad_set_type_instance(waa_batch* b, uint32_t node, uint32_t in
   return WAA_OK;
 }
 
+// every context of the reference builds its own PannerNode from its own PannerOptions (panner.rs:146-166, setters :545-641): one
+// complete set for one instance; any number of calls, the last one wins.  The panning model stays the node's (desc.i[0])
+waa_status waa_panner_set_options_instance(waa_batch* b, uint32_t node, uint32_t inst, const waa_panner_options* o) {
+  int e;
+  if ((e = check_node(b, node, WAA_NODE_PANNER)) || (e = check_unplanned(b))) return e;
+  if (inst != WAA_ALL_INSTANCES && inst >= b->n_inst)
+    return fail(WAA_ERR_INVALID_ARGUMENT, "instance %u out of range (PannerNode %u, %u instances)", inst, node, b->n_inst);
+  if (!o) return fail(WAA_ERR_INVALID_ARGUMENT, "PannerNode %u: null options", node);
+  if (o->reserved != 0) return fail(WAA_ERR_INVALID_ARGUMENT, "PannerNode %u: waa_panner_options.reserved is 0, got %d", node, o->reserved);
+  if (o->distance_model < WAA_DISTANCE_LINEAR || o->distance_model > WAA_DISTANCE_EXPONENTIAL)
+    return fail(WAA_ERR_INVALID_ARGUMENT, "bad distance model");
+  if ((e = check_panner_values(o->ref_distance, o->max_distance, o->rolloff_factor, o->cone_outer_gain))) return e;
+  Node& n = b->nodes[node];
+  if (inst == WAA_ALL_INSTANCES) {  // (the shared set: instances with a set of their own keep it)
+    n.desc.i[1] = o->distance_model;
+    n.desc.d[0] = o->ref_distance;
+    n.desc.d[1] = o->max_distance;
+    n.desc.d[2] = o->rolloff_factor;
+    n.desc.d[3] = o->cone_inner_angle;
+    n.desc.d[4] = o->cone_outer_angle;
+    n.desc.d[5] = o->cone_outer_gain;
+    return WAA_OK;
+  }
+  if (n.panner_inst_set.empty()) {
+    n.panner_inst_opt.assign(b->n_inst, waa_panner_options{});
+    n.panner_inst_set.assign(b->n_inst, 0);
+  }
+  n.panner_inst_opt[inst] = *o;
+  n.panner_inst_set[inst] = 1;
+  return WAA_OK;
+}
+
 // AudioParam::set_value_at_time & co. (param.rs:428-596) on a param of the batch; evaluated at plan time
 waa_status waa_param_schedule_event(waa_batch* b, uint32_t node, uint32_t param, uint32_t inst, int32_t type, float value,
                                     double time, double aux, const float* curve, uint32_t n_curve) {

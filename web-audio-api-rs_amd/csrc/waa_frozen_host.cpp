@@ -529,10 +529,17 @@ int plan_hrtf(waa_batch* b, uint32_t id, int src_id) {
     varies |= !ps.blocks.empty();
     if (ps.dev_tl) return fail(WAA_ERR_INVALID_STATE, "internal: device-side automation on an HRTF panner param");
   }
+  // one option set per instance, and the sets differ: a row per instance even where the fifteen params are shared
+  const bool options_differ = n.panner_options_differ();
+  if (options_differ) {
+    shared = false;
+    note_panner_options(b, id, n);
+  }
   const uint32_t rows = shared ? 1u : b->n_inst, per_row = varies ? b->n_quanta : 1u;
   std::vector<HrtfQ> table((size_t)rows * per_row);
   std::map<std::tuple<float, float, float>, std::pair<std::array<int, 3>, std::array<float, 3>>> located;
   for (uint32_t i = 0; i < rows; i++) {
+    const waa_panner_options po = n.panner_options_of(i);
     std::vector<std::vector<float>> pv(15);
     for (int k = 0; k < 15; k++) pv[k] = param_per_quantum(b, n.params[k], i, nullptr);
     for (uint32_t q = 0; q < per_row; q++) {
@@ -560,7 +567,7 @@ int plan_hrtf(waa_batch* b, uint32_t id, int src_id) {
         r.v[k] = it->second.first[(size_t)k];
         r.w[k] = it->second.second[(size_t)k];
       }
-      r.gain = cone_gain(n.desc, spos, so, lp) * dist_gain(n.desc, spos, lp);
+      r.gain = cone_gain(po, spos, so, lp) * dist_gain(po, spos, lp);
       r.pad = 0;
     }
   }

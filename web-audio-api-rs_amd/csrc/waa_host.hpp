@@ -20,7 +20,7 @@
 #include <tuple>
 #include <vector>
 
-#include "../../include/waa_hip.h"
+#include "../../include/waa_hip_device.h"
 #include "waa_internal.hpp"
 
 struct waa_batch;
@@ -235,6 +235,24 @@ struct Node {
     return false;
   }
   int biquad_shared_type() const { return per_inst_type() ? biquad_type_of(0) : desc.i[0]; }  // (only where !biquad_types_differ())
+  // panner: one option set per instance (waa_panner_set_options_instance): [n_inst] once the first instance has its own set; an
+  // instance whose flag is clear uses the shared one (desc.i[1], desc.d[0..5]).  The planner asks panner_options_differ(): a node
+  // whose instances all resolve to one set plans exactly as a shared node of that set.
+  std::vector<waa_panner_options> panner_inst_opt;
+  std::vector<uint8_t> panner_inst_set;
+  waa_panner_options panner_options_of(uint32_t inst) const {
+    if (!panner_inst_set.empty() && panner_inst_set[inst]) return panner_inst_opt[inst];
+    return waa_panner_options{desc.i[1], 0, desc.d[0], desc.d[1], desc.d[2], desc.d[3], desc.d[4], desc.d[5]};
+  }
+  bool panner_options_differ() const {
+    if (panner_inst_set.empty()) return false;
+    const waa_panner_options first = panner_options_of(0);  // (no padding: eight 8-byte-aligned fields in 56 bytes)
+    for (size_t i = 1; i < panner_inst_set.size(); i++) {
+      const waa_panner_options o = panner_options_of((uint32_t)i);
+      if (std::memcmp(&o, &first, sizeof o) != 0) return true;
+    }
+    return false;
+  }
   // analyser (control side state): the pulls of ALL instances are computed by one launch and cached until the next render
   // (current_time after an offline render never changes: repeated pulls return the same data, analysis.rs:354-357)
   struct AnBatch {
@@ -695,6 +713,16 @@ inline int check_unplanned(waa_batch* b) {
   if (b->planned) return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - the batch is frozen once rendering has started");
   return 0;
 }
+// PannerOptions' values (panner.rs:408-428, 20-33): waa_batch_create's check of a PANNER node's d[0..5], and that of
+// waa_panner_set_options_instance
+inline int check_panner_values(double ref_distance, double max_distance, double rolloff_factor, double cone_outer_gain) {
+  if (!(ref_distance >= 0.)) return fail(WAA_ERR_INVALID_ARGUMENT, "RangeError - refDistance cannot be negative");
+  if (!(max_distance > 0.)) return fail(WAA_ERR_INVALID_ARGUMENT, "RangeError - maxDistance must be strictly positive");
+  if (!(rolloff_factor >= 0.)) return fail(WAA_ERR_INVALID_ARGUMENT, "RangeError - rolloffFactor cannot be negative");
+  if (!(cone_outer_gain >= 0. && cone_outer_gain <= 1.))
+    return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - coneOuterGain must be in the range [0, 1]");
+  return 0;
+}
 inline int check_channel_count(uint32_t n_ch) {
   if (n_ch == 0 || n_ch > WAA_MAX_CHANNELS) return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - Invalid number of channels");
   return 0;
@@ -726,8 +754,8 @@ struct V3 {
 constexpr float PI_F = 3.14159265358979323846f;
 void azimuth_elevation(V3 sp, V3 lp, V3 lf, V3 lu, float* az, float* el);               // spatial.rs / panner.rs
 float spatial_angle(V3 sp, V3 so, V3 lp);
-float cone_gain(const waa_node_desc& d, V3 sp, V3 so, V3 lp);
-float dist_gain(const waa_node_desc& d, V3 sp, V3 lp);
+float cone_gain(const waa_panner_options& o, V3 sp, V3 so, V3 lp);
+float dist_gain(const waa_panner_options& o, V3 sp, V3 lp);
 // AudioBufferSourceNode scheduler: port of audio_buffer_source.rs:422-845
 void schedule_source(const waa_batch* b, const SourceSched& cfg, uint64_t frames, float buf_sr, bool has_buffer,
                      const std::vector<float>& rate_q, const std::vector<float>& detune_q, SchedOut* out);
@@ -761,6 +789,8 @@ int plan_oversampler(waa_batch* b, uint32_t id, int src_id);
 int plan_hrtf(waa_batch* b, uint32_t id, int src_id);
 bool hrtf_sphere_loaded();
 void plan_note(waa_batch* b, const char* fmt, ...);
+// the plan's line for a PannerNode whose instances differ in their option sets, once per node (waa_plan_ops.cpp)
+void note_panner_options(waa_batch* b, uint32_t id, const Node& n);
 int slot_for(waa_batch* b, const char* name);
 // one launch: the profiling events around it when the batch is profiled and the launch has a slot, the error check behind it
 template <typename L>

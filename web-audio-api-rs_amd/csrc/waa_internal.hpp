@@ -698,6 +698,13 @@ struct BiquadHpDesc {
 void launch_biquad_hp(const BiquadHpDesc& d, void* stream);
 
 // ---- per-frame panner geometry for an audio-rate AudioListener (waa_panner.hip; panner.rs:720-897) ----
+// the option set of one instance (waa_panner_set_options_instance), as panner_geom_inst_kernel reads it: 40 bytes
+struct PannerOptRow {
+  double ref_distance, max_distance, rolloff;
+  float cone_inner, cone_outer, cone_outer_gain;
+  int32_t distance_model;
+};
+static_assert(sizeof(PannerOptRow) == 40, "three doubles, three floats, one int32");
 struct PannerGeomDesc {
   ParamRef p[15];          // WAA_PARAM_PANNER_* / WAA_PARAM_LISTENER_* in id order
   const uint8_t* single;   // [rows][single_stride]: 1 = all nine listener params are single-valued in this quantum
@@ -710,6 +717,7 @@ struct PannerGeomDesc {
   double ref_distance, max_distance, rolloff;
   float cone_inner, cone_outer, cone_outer_gain;
   int32_t pad;
+  const PannerOptRow* opts;  // [rows], rows = n_inst: one option set per instance (panner_geom_inst_kernel; the scalars above unused); null: the scalars
 };
 void launch_panner_geom(const PannerGeomDesc& d, void* stream);
 

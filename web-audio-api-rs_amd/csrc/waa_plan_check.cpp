@@ -89,6 +89,7 @@ static StepIo step_io_raw(const Step& st) {
       break;
     case StepKind::PannerGeom:
       for (int k = 0; k < 15; k++) io_param(st.geom.p[k], io);
+      if (st.geom.opts) io.reads.push_back(st.geom.opts);  // one option set per instance (uploaded at plan time)
       io.writes.push_back(st.geom.az);
       io.writes.push_back(st.geom.gl_mono);
       io.writes.push_back(st.geom.gr_mono);

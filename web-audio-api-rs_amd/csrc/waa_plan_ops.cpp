@@ -26,6 +26,30 @@ static void note_biquad_types(waa_batch* b, uint32_t id, const Node& n, const ch
   plan_note(b, "%s", line.c_str());
 }
 
+// The plan's line for a PannerNode whose instances differ in their option sets (waa_panner_set_options_instance): the node, the
+// distinct sets and the instances per distance model.  One line per node, however often its geometry is evaluated.
+void note_panner_options(waa_batch* b, uint32_t id, const Node& n) {
+  static const char* const names[3] = {"linear", "inverse", "exponential"};
+  uint32_t cnt[3] = {};
+  std::set<std::string> distinct;
+  for (uint32_t i = 0; i < b->n_inst; i++) {
+    const waa_panner_options o = n.panner_options_of(i);
+    cnt[o.distance_model == WAA_DISTANCE_LINEAR ? 0 : o.distance_model == WAA_DISTANCE_INVERSE ? 1 : 2]++;
+    distinct.emplace(reinterpret_cast<const char*>(&o), sizeof o);
+  }
+  std::string line = "panner node " + std::to_string(id) + ": one option set per instance: " + std::to_string(distinct.size()) + " distinct set(s) (";
+  const char* sep = "";
+  for (int t = 0; t < 3; t++)
+    if (cnt[t]) {
+      line += std::string(sep) + names[t] + " x" + std::to_string(cnt[t]);
+      sep = " ";
+    }
+  line += ")";
+  for (const std::string& l : b->plan_log)
+    if (l == line) return;
+  plan_note(b, "%s", line.c_str());
+}
+
 // Emit the fused ops of node `id` given the running channel count.
 int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector<OpDesc>& ops, int* out_nch) {
   Node& n = b->nodes[id];
@@ -350,6 +374,11 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
           if (e) return e;
           if (k >= 6 && ps.dev_tl) g.dev_len[k - 6] = ps.dev_lens;  // slice lengths come from the device replay
         }
+        // one option set per instance, and the sets differ: a row per instance even under one automation shared by the batch —
+        // 7 tables x 4 B per frame and instance (a row map over the distinct sets would change every consumer)
+        const bool options_differ = n.panner_options_differ();
+        const bool shared_params = shared;
+        if (options_differ) shared = false;
         g.rows = shared ? 1u : b->n_inst;
         g.n_frames = (uint64_t)b->n_quanta * RQ;
         std::vector<uint8_t> single((size_t)g.rows * b->n_quanta, 1);
@@ -380,14 +409,27 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
         g.gr_stereo = tabs[4];
         g.dg = tabs[5];
         g.cg = tabs[6];
-        g.distance_model = n.desc.i[1];
-        g.ref_distance = n.desc.d[0];
-        g.max_distance = n.desc.d[1];
-        g.rolloff = n.desc.d[2];
-        g.cone_inner = (float)n.desc.d[3];
-        g.cone_outer = (float)n.desc.d[4];
-        g.cone_outer_gain = (float)n.desc.d[5];
-        gs.profile_slot = slot_for(b, "panner_geom_kernel");
+        auto opt_row = [](const waa_panner_options& po) {
+          return PannerOptRow{po.ref_distance,           po.max_distance,           po.rolloff_factor,         (float)po.cone_inner_angle,
+                              (float)po.cone_outer_angle, (float)po.cone_outer_gain, po.distance_model};
+        };
+        const PannerOptRow r0 = opt_row(n.panner_options_of(0));  // (the set of every instance unless they differ)
+        g.distance_model = r0.distance_model;
+        g.ref_distance = r0.ref_distance;
+        g.max_distance = r0.max_distance;
+        g.rolloff = r0.rolloff;
+        g.cone_inner = r0.cone_inner;
+        g.cone_outer = r0.cone_outer;
+        g.cone_outer_gain = r0.cone_outer_gain;
+        if (options_differ) {
+          std::vector<PannerOptRow> rows(b->n_inst);
+          for (uint32_t i = 0; i < b->n_inst; i++) rows[i] = opt_row(n.panner_options_of(i));
+          PannerOptRow* d_rows = nullptr;
+          if ((e = dev_upload(b, &d_rows, rows))) return e;
+          g.opts = d_rows;
+          note_panner_options(b, id, n);
+        }
+        gs.profile_slot = slot_for(b, options_differ ? "panner_geom_inst_kernel" : "panner_geom_kernel");
         b->steps.push_back(gs);
         auto ref = [&](float* base) {
           ParamRef r{};
@@ -401,8 +443,8 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
         o.p2 = ref(nch == 1 ? g.gr_mono : g.gr_stereo);
         o.p3 = ref(g.dg);
         o.p4 = ref(g.cg);
-        plan_note(b, "panner node %u: audio-rate AudioListener automation -> per-frame geometry on the device (%u table row(s))", id,
-                  g.rows);
+        plan_note(b, "panner node %u: audio-rate AudioListener automation -> per-frame geometry on the device (%u table row(s))%s", id,
+                  g.rows, options_differ && shared_params ? "; per instance because of the options" : "");
         ops.push_back(o);
         break;
       }
@@ -411,7 +453,10 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
       const uint32_t cnt = mode == 0 ? 1 : b->n_quanta;
       const int vmode = mode == 0 ? 0 : 1;
       std::vector<float> az((size_t)b->n_inst * cnt), gl(az.size()), gr(az.size()), dg(az.size()), cg(az.size());
+      // one option set per instance: every row from its instance's set (equal sets everywhere: the rows of a shared node)
+      if (n.panner_options_differ()) note_panner_options(b, id, n);
       for (uint32_t i = 0; i < b->n_inst; i++) {
+        const waa_panner_options po = n.panner_options_of(i);
         std::vector<std::vector<float>> pv(15);
         for (int k = 0; k < 15; k++) pv[k] = param_per_quantum(b, n.params[k], i, nullptr);
         for (uint32_t k = 0; k < cnt; k++) {
@@ -431,8 +476,8 @@ int emit_node_ops(waa_batch* b, uint32_t id, int cur_nch, bool head, std::vector
           az[ix] = a;
           gl[ix] = cosf(x * PI_F / 2.f);
           gr[ix] = sinf(x * PI_F / 2.f);
-          dg[ix] = dist_gain(n.desc, sp, lp);
-          cg[ix] = cone_gain(n.desc, sp, so, lp);
+          dg[ix] = dist_gain(po, sp, lp);
+          cg[ix] = cone_gain(po, sp, so, lp);
         }
       }
       int e;

@@ -131,20 +131,20 @@ float spatial_angle(V3 sp, V3 so, V3 lp) {
   V3 sl = normalized(rel);
   return std::fabs(180.f * acosf(dot(sl, son)) / PI_F);
 }
-float cone_gain(const waa_node_desc& d, V3 sp, V3 so, V3 lp) {
-  float in = (float)std::fabs(d.d[3]) / 2.f, out = (float)std::fabs(d.d[4]) / 2.f;
+float cone_gain(const waa_panner_options& o, V3 sp, V3 so, V3 lp) {
+  float in = (float)std::fabs(o.cone_inner_angle) / 2.f, out = (float)std::fabs(o.cone_outer_angle) / 2.f;
   if (in >= 180.f && out >= 180.f) return 1.f;
-  float cog = (float)d.d[5];
+  float cog = (float)o.cone_outer_gain;
   float a = spatial_angle(sp, so, lp);
   if (a < in) return 1.f;
   if (a >= out) return cog;
   float x = (a - in) / (out - in);
   return (1.f - x) + cog * x;
 }
-float dist_gain(const waa_node_desc& d, V3 sp, V3 lp) {
+float dist_gain(const waa_panner_options& o, V3 sp, V3 lp) {
   double distance = (double)std::sqrt(sqlen(sub(sp, lp)));
-  double ref = d.d[0], maxd = d.d[1], roll = d.d[2], g;
-  switch (d.i[1]) {
+  double ref = o.ref_distance, maxd = o.max_distance, roll = o.rolloff_factor, g;
+  switch (o.distance_model) {
     case WAA_DISTANCE_LINEAR: {
       double rf = roll < 0. ? 0. : roll > 1. ? 1. : roll;
       double lo = std::fmin(ref, maxd), hi = std::fmax(ref, maxd);

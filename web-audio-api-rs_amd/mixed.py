@@ -8,7 +8,8 @@ step for the Python mirror (round-5 review, missing 4): contexts built one by on
 channel configuration, connections), the context's format, the SHAPES of per-context payloads (an AudioBufferSource's channel count,
 length and rate, and on the device library the padded length of an IIRFilterNode's coefficients, which become per-instance sets of the
 batch) and the identity of payloads a batch shares (a convolver's impulse response, an oversampled shaper's curve, and on other bindings
-IIR coefficients, an oscillator's PeriodicWave and built-in type, a plain shaper's curve and a Biquad's type, which the device library takes per instance) — every bucket is merged into one
+IIR coefficients, an oscillator's PeriodicWave and built-in type, a plain shaper's curve, a Biquad's type and a PannerNode's distance and cone options
+(not its panning model, which shapes the plan), which the device library takes per instance) — every bucket is merged into one
 batch (per-context AudioBuffers, AudioParam values and automation, start / stop / loop settings become per-instance settings of the batch), rendered, and the AudioBuffers are handed back in the callers' order.
 Contexts with suspend callbacks render on their own (their callbacks may do anything)."""
 from __future__ import annotations
@@ -18,8 +19,8 @@ from typing import List, Sequence
 
 import numpy as np
 
-from .api import ALL, AudioBufferSourceNode, AudioParam, BiquadFilterNode, ConvolverNode, IIRFilterNode, OfflineAudioContext, OscillatorNode, RenderedBatch, \
-    WaveShaperNode, _ScheduledSource
+from .api import ALL, AudioBufferSourceNode, AudioParam, BiquadFilterNode, ConvolverNode, IIRFilterNode, OfflineAudioContext, OscillatorNode, PannerNode, \
+    RenderedBatch, WaveShaperNode, _ScheduledSource
 
 
 def _digest(a) -> str:
@@ -55,8 +56,13 @@ def _node_key(nd) -> tuple:
     if isinstance(nd, OscillatorNode) and nd.context._b.prefix == "waa_" and nd.type_of(0) != "custom":
         # ... and one built-in oscillator type per context; a context with a PeriodicWave stays apart from one without (below)
         ints = ("oscillator-type",) + ints[1:]
+    dbls = tuple(float(x) for x in d.d)
+    if isinstance(nd, PannerNode) and nd.context._b.prefix == "waa_":
+        # ... and one set of distance and cone options per context (i[1], d[0..5]); the panning model (i[0]) stays in the key
+        ints = ints[:1] + ("panner-options",) + ints[2:]
+        dbls = ("panner-options",) + dbls[6:]
     key = [type(nd).__name__, int(d.kind), int(d.channel_count), int(d.channel_count_mode), int(d.channel_interpretation),
-           ints, tuple(float(x) for x in d.d)]
+           ints, dbls]
     if isinstance(nd, ConvolverNode):  # (shared by the batch: another response is another batch)
         key.append(None if nd.buffer is None else (_digest(nd.buffer.data), float(nd.buffer.sample_rate)))
         pcm = getattr(nd, "_pcm", None)
@@ -162,6 +168,14 @@ def _merge(bucket: Sequence[OfflineAudioContext]) -> OfflineAudioContext:
             if not all(t == types[0] for t in types[1:]):
                 for i, t in enumerate(types):
                     cn.set_type(t, instance=i)
+        if isinstance(cn, PannerNode) and cn.context._b.prefix == "waa_":
+            # every context's effective option set becomes its instance's; equal sets everywhere: the node stays shared
+            sets = [nd.options_of(0) for nd in [cn] + others]
+            cn._inst_options = {}
+            cn.set_options(**sets[0])
+            if not all(o == sets[0] for o in sets[1:]):
+                for i, o in enumerate(sets):
+                    cn.set_options(instance=i, **o)
         if isinstance(cn, WaveShaperNode) and _curve(cn) is not None:
             # every context's effective curve (_curve) becomes its instance's; equal curves everywhere: the node stays shared
             curves = [_curve(nd) for nd in [cn] + others]
