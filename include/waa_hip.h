@@ -172,6 +172,9 @@ enum {
  *                 the interpretation is free (default: speakers).
  *                 Both kinds are rendered by static plans only: WAA_ERR_OUT_OF_SCOPE inside a feedback loop and in a
  *                 graph that needs exact per-quantum channel counts.
+ *     DYNAMICS_COMPRESSOR  i[0] = meter, on the device library only: 0 = off, 1 = keep DynamicsCompressorNode::reduction()
+ *                 after every render quantum (waa_compressor_get_reduction / _series, waa_hip_device.h); anything else
+ *                 is WAA_ERR_INVALID_ARGUMENT
  *     DELAY       d[0] = max_delay_time in seconds (0 = the default, 1 s); must be > 0 and < 180
  *                 (NotSupportedError, delay.rs:290-293).  Graph cycles through a DelayNode are rendered (the delay
  *                 is clamped to one render quantum inside a loop, delay.rs:693-701); cycles without one are muted.

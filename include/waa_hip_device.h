@@ -163,6 +163,30 @@ typedef struct waa_panner_options {
 } waa_panner_options;
 waa_status waa_panner_set_options_instance(waa_batch* batch, uint32_t node, uint32_t instance, const waa_panner_options* options);
 
+/* DynamicsCompressorNode::reduction (src/node/dynamics_compressor.rs:304-306): the gain reduction in dB that the render thread
+ * stored when it finished a render quantum — `-detector_value + makeup_gain` of the quantum's last frame (:440, stored at :450;
+ * 0 before anything is rendered, :249).  Replaces polling one context at a time while it renders: a batched offline render
+ * keeps the WHOLE trace, the value the reference would return after every render quantum, for every context — a gain-reduction
+ * curve per clip, for plots, labels of a data set, choosing a threshold per clip.
+ *
+ * The meter is opt-in per node: waa_node_desc.i[0] of a WAA_NODE_DYNAMICS_COMPRESSOR is 0 (off, the default) or 1 (keep the
+ * trace); waa_batch_create refuses any other value (WAA_ERR_INVALID_ARGUMENT, naming the node and the value).  A node with the
+ * meter off plans and renders exactly as before (the same three launches, the same plan text).  With the meter on the plan
+ * allocates [n_instances][n_quanta] floats and the node's step ends with a fourth launch, compressor_meter_kernel: one f32
+ * negation and one f32 add per value, in the reference's order, from the detector's values and the make-up gain of the
+ * quantum's own block constants.  Every render writes the trace again; waa_batch_rearm keeps the buffer.
+ *
+ * waa_compressor_get_reduction: the value after the last rendered quantum, for one instance.
+ * waa_compressor_get_reduction_series: dst[n_instances][n_quanta], row q = the value after quantum q; n_quanta must be the
+ * batch's ceil(length / 128), anything else is WAA_ERR_INVALID_ARGUMENT (as are a NULL batch or destination, a node index and
+ * an instance out of range).  Both are WAA_ERR_INVALID_STATE (InvalidStateError) for a node of another kind, for a compressor
+ * whose meter is off (the message names i[0]), before the batch has rendered and while a ranged render (waa_render_range) is
+ * still in front of its last range.  A pageable destination is filled through the batch's pinned staging block, like every
+ * download.  A metered node that does not reach the destination is not rendered: its values are the initial 0.
+ * Out of scope: the trace of a batch merged from single contexts, and waa_render_sharded. */
+waa_status waa_compressor_get_reduction(waa_batch* batch, uint32_t node, uint32_t instance, float* value);
+waa_status waa_compressor_get_reduction_series(waa_batch* batch, uint32_t node, float* dst, uint32_t n_quanta);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,14 @@ frames x 4 bytes: level reads nch and writes 1, apply reads 1 + nch and writes n
 cycles per sample per wavefront (time x clock / frames) — every wavefront walks the whole render, so the number does not depend on
 the batch size until the wavefronts outnumber the SIMDs.
 
-    python tools/compressor_probe.py [--instances 1024] [--seconds 10] [--out profiles/compressor_probe.json]"""
+    python tools/compressor_probe.py [--instances 1024] [--seconds 10] [--out profiles/compressor_probe.json]
+
+--meter: what the reduction trace costs (DynamicsCompressorNode(meter=True): a fourth launch, compressor_meter_kernel).  Per channel
+count two batches, meter off and meter on, built in the same process and timed ALTERNATELY (off, on, off, on, ...: ROUNDS rounds of
+the protocol above each), so that the meter-off leg is the comparison and not an earlier file's number; the meter-off wall time is
+also set against the spread of profiles/compressor_probe.json and a difference beyond it is reported as it is.
+
+    python tools/compressor_probe.py --meter [--out profiles/compressor_reduction_probe.json]"""
 import argparse
 import json
 import os
@@ -52,13 +59,55 @@ def timed(ctx):
     return dict(wall_ms_median=walls[len(walls) // 2], wall_ms_min=walls[0], wall_ms_max=walls[-1], kernels_ms=kernels)
 
 
-def compressor(hip, noise, n_inst, frames, n_ch):
+def compressor(hip, noise, n_inst, frames, n_ch, meter=False):
     ctx = waa.OfflineAudioContext(n_ch, frames, SR, n_instances=n_inst, binding=hip, device=0)
     src = ctx.create_buffer_source()
     src.adopt_device_buffer(noise.data_ptr(), n_ch, frames, SR)
-    src.connect(ctx.create_dynamics_compressor()).connect(ctx.destination())
+    src.connect(ctx.create_dynamics_compressor(meter=meter)).connect(ctx.destination())
     src.start()
     return ctx
+
+
+ROUNDS = 3
+
+
+def median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def meter_leg(hip, rec, noises, n, frames):
+    """meter off / meter on, alternately, per channel count; rec["lines"]: one entry per channel count"""
+    parent_path = os.path.join(ROOT, "profiles", "compressor_probe.json")
+    parent = {l["channels"]: l for l in json.load(open(parent_path))["lines"]} if os.path.exists(parent_path) else {}
+    for n_ch, noise in noises:
+        legs = {False: compressor(hip, noise, n, frames, n_ch, False), True: compressor(hip, noise, n, frames, n_ch, True)}
+        plan = [l for l in legs[True].plan_describe().splitlines() if l.startswith("compressor node")]
+        rounds = {False: [], True: []}
+        for _ in range(ROUNDS):
+            for meter in (False, True):
+                rounds[meter].append(timed(legs[meter]))
+        for ctx in legs.values():
+            ctx.close()
+        off = median([r["wall_ms_median"] for r in rounds[False]])
+        on = median([r["wall_ms_median"] for r in rounds[True]])
+        meter_ms = median([r["kernels_ms"]["compressor_meter_kernel"] for r in rounds[True]])
+        assert all("compressor_meter_kernel" not in r["kernels_ms"] for r in rounds[False])
+        line = dict(channels=n_ch, plan=plan, rounds=ROUNDS, meter_kernel_ms=meter_ms, wall_ms_meter_off=off, wall_ms_meter_on=on,
+                    wall_ms_difference=on - off, kernels_total_ms_meter_off=median([sum(r["kernels_ms"].values()) for r in rounds[False]]),
+                    kernels_total_ms_meter_on=median([sum(r["kernels_ms"].values()) for r in rounds[True]]),
+                    trace_values=n * (frames // 128), trace_mb=n * (frames // 128) * 4 / 1e6,
+                    meter_off_rounds=rounds[False], meter_on_rounds=rounds[True])
+        if n_ch in parent and n == 1024 and frames == 480000:
+            p = parent[n_ch]
+            line["parent_probe"] = dict(wall_ms_median=p["wall_ms_median"], wall_ms_min=p["wall_ms_min"], wall_ms_max=p["wall_ms_max"],
+                                        meter_off_within_its_spread=bool(p["wall_ms_min"] <= off <= p["wall_ms_max"]),
+                                        meter_off_minus_its_median_ms=off - p["wall_ms_median"])
+        rec["lines"].append(line)
+        print(f"compressor {n_ch}ch: meter off {off:.3f} ms | meter on {on:.3f} ms ({on - off:+.3f}) | compressor_meter_kernel {meter_ms:.4f} ms"
+              + (f" | parent probe {line['parent_probe']['wall_ms_median']:.3f} ms [{line['parent_probe']['wall_ms_min']:.3f}, "
+                 f"{line['parent_probe']['wall_ms_max']:.3f}]: meter off {'inside' if line['parent_probe']['meter_off_within_its_spread'] else 'OUTSIDE'} its spread"
+                 if "parent_probe" in line else ""), flush=True)
 
 
 def main():
@@ -66,8 +115,10 @@ def main():
     ap.add_argument("--instances", type=int, default=1024)
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--clock-mhz", type=float, default=2400.0, help="engine clock if torch does not report one (MI355X: 2400)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "compressor_probe.json"))
+    ap.add_argument("--meter", action="store_true", help="the reduction trace: meter off / meter on alternately (see above)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "compressor_reduction_probe.json" if args.meter else "compressor_probe.json")
     n, frames = args.instances, int(args.seconds * SR) // 128 * 128
     hip = waa.default_binding()
     props = torch.cuda.get_device_properties(0)
@@ -79,6 +130,10 @@ def main():
     torch.cuda.synchronize()
     rec = dict(instances=n, frames=frames, sample_rate=SR, warmup=WARMUP, steps=STEPS, plane_gb=plane_gb,
                device=torch.cuda.get_device_name(0), clock_mhz=clock_mhz, lines=[])
+    if args.meter:
+        meter_leg(hip, rec, ((1, mono), (2, stereo)), n, frames)
+        write(rec, args.out)
+        return
     c2, _ = bench.build_workload(waa, hip, "c2", n, frames, 0, stereo.data_ptr())
     t_c2 = timed(c2)
     c2.close()
@@ -103,11 +158,15 @@ def main():
               f"per byte) | detector {det:.3f} ms ({line['detector']['ns_per_sample']:.2f} ns / sample"
               + f", {line['detector']['cycles_per_sample_per_wavefront']:.1f} cycles at {clock_mhz:.0f} MHz"
               + f") | apply {apply_:.3f} ms ({line['apply']['fraction_of_c2_rate_per_byte']:.2f})", flush=True)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
+    write(rec, args.out)
+
+
+def write(rec, path):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
         json.dump(rec, f, indent=1, sort_keys=True)
         f.write("\n")
-    print("wrote", args.out)
+    print("wrote", path)
 
 
 if __name__ == "__main__":

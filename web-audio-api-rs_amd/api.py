@@ -210,6 +210,8 @@ ABI_DEVICE = {
     "biquad_set_type_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, C.c_int32]),
     "oscillator_set_type_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, C.c_int32]),
     "panner_set_options_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _VP]),
+    "compressor_get_reduction": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP]),
+    "compressor_get_reduction_series": (C.c_int32, [_VP, C.c_uint32, _FP, C.c_uint32]),
 }
 
 
@@ -1051,12 +1053,16 @@ class StereoPannerNode(AudioNode):
 
 class DynamicsCompressorNode(AudioNode):
     """src/node/dynamics_compressor.rs — the five k-rate AudioParams and the channel-config constraints; the node itself is
-    rendered by the library (waa_compressor.hip), nothing is computed here."""
+    rendered by the library (waa_compressor.hip), nothing is computed here.
+
+    meter=True (the device library only) keeps `reduction()` after every render quantum of every context: `reduction_series()`
+    is the whole trace, `reduction()` / `reduction_all()` its last row, as the reference's method returns it after the render."""
     kind = NODE_DYNAMICS_COMPRESSOR
     default_channel_config = (2, "clamped-max", "speakers")
 
     def __init__(self, ctx, attack: float = 0.003, knee: float = 30.0, ratio: float = 12.0, release: float = 0.25,
-                 threshold: float = -24.0, **kw):
+                 threshold: float = -24.0, meter: bool = False, **kw):
+        self.meter = bool(meter)
         # DynamicsCompressorNode::new asserts both before anything else (dynamics_compressor.rs:184-185)
         self._assert_valid_channel_count(kw.get("channel_count") or 2)
         self._assert_valid_channel_count_mode(kw.get("channel_count_mode") or "clamped-max")
@@ -1085,6 +1091,67 @@ class DynamicsCompressorNode(AudioNode):
     def set_channel_count_mode(self, v: str):
         self._assert_valid_channel_count_mode(v)
         super().set_channel_count_mode(v)
+
+    def _fill_desc(self, d):
+        if self.meter and self.context._b.prefix != "waa_":
+            raise WaaError(4, "the reduction meter of a DynamicsCompressorNode (meter=True) is a feature of the device library; this "
+                              "binding keeps no trace")
+        d.i[0] = 1 if self.meter else 0
+
+    # -- reduction (dynamics_compressor.rs:304-306) --------------------------------------------------------------------
+    def _metered(self):
+        if not self.meter:
+            raise ValueError("this DynamicsCompressorNode keeps no reduction: create it with meter=True")
+
+    def _last_row(self, instance):
+        """the value after the last rendered quantum: [n_instances] (instance None) or one float.  Before the render, outside a
+        suspend callback: the reference's initial 0 (:249), without a library call; inside a suspend_sync callback at quantum
+        q > 0: the value after quantum q - 1, from a prefix render like an analyser pull"""
+        self._metered()
+        ctx = self.context
+        if ctx._now_q > 0 and ctx._handle is None:
+            q = ctx._now_q
+            with ctx._prefix_render(q):  # (a batch of q quanta: its last row is the value after quantum q - 1)
+                return self._read_last(instance, q)
+        if ctx._handle is None or not ctx._rendered:
+            return 0.0 if instance is not None else np.zeros(ctx.n_instances, np.float32)
+        return self._read_last(instance, (ctx.length + RENDER_QUANTUM_SIZE - 1) // RENDER_QUANTUM_SIZE)
+
+    def _read_last(self, instance, n_quanta):
+        ctx = self.context
+        if instance is not None:
+            v = C.c_float()
+            ctx._b.check(ctx._b.compressor_get_reduction(ctx._handle, self.id, int(instance), C.byref(v)))
+            return float(v.value)
+        # (every context's last value in ONE transfer: the trace's last column)
+        rows = np.zeros((ctx.n_instances, n_quanta), np.float32)
+        ctx._b.check(ctx._b.compressor_get_reduction_series(ctx._handle, self.id, _fp(rows), n_quanta))
+        return np.ascontiguousarray(rows[:, -1])
+
+    def reduction(self, instance: int = 0) -> float:
+        """DynamicsCompressorNode::reduction of one context: the gain reduction in dB after the last rendered quantum"""
+        return self._last_row(int(instance))
+
+    def reduction_all(self) -> np.ndarray:
+        """[n_instances]: `reduction()` of every context"""
+        return self._last_row(None)
+
+    def reduction_series(self, out=None) -> np.ndarray:
+        """[n_instances][n_quanta]: row q is what `reduction()` returns after render quantum q (one gather launch per render, kept
+        on the device until it is read).  Only after start_rendering_sync."""
+        self._metered()
+        ctx = self.context
+        if ctx._handle is None or ctx._now_q > 0:
+            raise WaaError(3, "InvalidStateError - the reduction trace is only available after start_rendering_sync")
+        n_quanta = (ctx.length + RENDER_QUANTUM_SIZE - 1) // RENDER_QUANTUM_SIZE
+        shape = (ctx.n_instances, n_quanta)
+        if out is None:
+            out = np.zeros(shape, np.float32)
+        if not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np.float32 or not out.flags.c_contiguous:
+            # (the library writes n_quanta values per context through the raw pointer: a wrong buffer is a silent out-of-bounds write)
+            raise ValueError(f"out: expected a C-contiguous float32 array of shape {shape}")
+        ctx._b.check(ctx._b.compressor_get_reduction_series(ctx._handle, self.id, _fp(out), n_quanta))
+        return out
 
 
 class AudioListener:
@@ -1802,6 +1869,7 @@ class OfflineAudioContext:
         return PeriodicWave(self, **kw)
 
     def create_dynamics_compressor(self, **kw):
+        """meter=True: keep reduction() after every render quantum (DynamicsCompressorNode.reduction_series)"""
         return DynamicsCompressorNode(self, **kw)
 
     def create_channel_splitter(self, number_of_outputs: int = 6, **kw):

@@ -189,6 +189,9 @@ static int init_node(waa_batch* b, uint32_t i) {
         return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - DynamicsCompressorNode channel count cannot be greater than two");
       if (n.mode == WAA_COUNT_MODE_MAX)
         return fail(WAA_ERR_NOT_SUPPORTED, "NotSupportedError - DynamicsCompressorNode channel count mode cannot be set to max");
+      // the meter: i[0] = 1 keeps reduction() after every quantum (waa_compressor_get_reduction, include/waa_hip_device.h)
+      if (n.desc.i[0] != 0 && n.desc.i[0] != 1)
+        return fail(WAA_ERR_INVALID_ARGUMENT, "DynamicsCompressorNode %u: i[0] is 0 (no meter) or 1 (keep the reduction trace), got %d", i, n.desc.i[0]);
       P(WAA_PARAM_COMPRESSOR_THRESHOLD).init(n_inst, -24.f, -100.f, 0.f);
       P(WAA_PARAM_COMPRESSOR_KNEE).init(n_inst, 30.f, 0.f, 40.f);
       P(WAA_PARAM_COMPRESSOR_RATIO).init(n_inst, 12.f, 1.f, 20.f);

@@ -380,6 +380,50 @@ waa_status waa_panner_set_options_instance(waa_batch* b, uint32_t node, uint32_t
   return WAA_OK;
 }
 
+// DynamicsCompressorNode::reduction (dynamics_compressor.rs:304-306): what the render thread stored after a quantum (:440, :450).
+// The trace of a node with the meter on is on the device after every render ([n_inst][n_quanta], compressor_meter_kernel): both
+// getters copy out of it, rows [i0, i1) x quanta [q0, n_quanta), through the batch's pinned staging block if `dst` is pageable.
+static int compressor_reduction_rows(waa_batch* b, uint32_t node, uint32_t i0, uint32_t i1, uint32_t q0, float* dst) {
+  if (node >= b->nodes.size()) return fail(WAA_ERR_INVALID_ARGUMENT, "node %u out of range", node);
+  const Node& n = b->nodes[node];
+  if (n.desc.kind != WAA_NODE_DYNAMICS_COMPRESSOR)
+    return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - node %u is not a DynamicsCompressorNode: it has no reduction", node);
+  if (!n.comp_meter())
+    return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - DynamicsCompressorNode %u was created without its meter: waa_node_desc.i[0] = 1 keeps the "
+                                       "reduction trace (i[0] is %d)", node, n.desc.i[0]);
+  if (b->ranged && b->ctl_q < b->n_quanta)
+    return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - DynamicsCompressorNode %u: a ranged render is in progress (suspended in front of quantum %u); the "
+                                       "reduction is available once the last range is rendered", node, b->ctl_q);
+  if (!b->planned || !b->rendered)
+    return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - DynamicsCompressorNode %u: nothing rendered yet, no reduction to read", node);
+  if (!dst) return fail(WAA_ERR_INVALID_ARGUMENT, "DynamicsCompressorNode %u: null destination", node);
+  const size_t width = (size_t)(b->n_quanta - q0) * sizeof(float), rows = i1 - i0;
+  if (!n.d_comp_red) {
+    // the node does not reach the destination: it is not rendered, the value is the initial one (:249)
+    for (size_t r = 0; r < rows; r++) std::memset((char*)dst + r * width, 0, width);
+    return WAA_OK;
+  }
+  HIP_TRY(hipSetDevice(b->device));
+  if (int es = settle_loops(b)) return es;  // (a render that was repeated with settled loop blocks wrote the trace again)
+  if (int e = xfer_d2h(b, dst, width, n.d_comp_red + (size_t)i0 * b->n_quanta + q0, (size_t)b->n_quanta * sizeof(float), width, rows)) return e;
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return WAA_OK;
+}
+
+waa_status waa_compressor_get_reduction(waa_batch* b, uint32_t node, uint32_t inst, float* value) {
+  if (!b) return fail(WAA_ERR_INVALID_ARGUMENT, "null batch");
+  if (inst >= b->n_inst) return fail(WAA_ERR_INVALID_ARGUMENT, "instance %u out of range (DynamicsCompressorNode %u, %u instances)", inst, node, b->n_inst);
+  return compressor_reduction_rows(b, node, inst, inst + 1, b->n_quanta - 1, value);  // (after the LAST rendered quantum)
+}
+
+waa_status waa_compressor_get_reduction_series(waa_batch* b, uint32_t node, float* dst, uint32_t n_quanta) {
+  if (!b) return fail(WAA_ERR_INVALID_ARGUMENT, "null batch");
+  if (n_quanta != b->n_quanta)
+    return fail(WAA_ERR_INVALID_ARGUMENT, "DynamicsCompressorNode %u: the reduction trace has one value per render quantum, %u for this batch (got n_quanta = %u)",
+                node, b->n_quanta, n_quanta);
+  return compressor_reduction_rows(b, node, 0, b->n_inst, 0, dst);
+}
+
 // AudioParam::set_value_at_time & co. (param.rs:428-596) on a param of the batch; evaluated at plan time
 waa_status waa_param_schedule_event(waa_batch* b, uint32_t node, uint32_t param, uint32_t inst, int32_t type, float value,
                                     double time, double aux, const float* curve, uint32_t n_curve) {

@@ -12,6 +12,7 @@
 //   compressor_level_kernel     parallel over time x context (streaming): x -> xL, one f32 plane per context
 //   compressor_detector_kernel  one LANE per context, 64 contexts per wavefront, serial in time: xL -> yL in place
 //   compressor_apply_kernel     parallel (streaming): yL, delayed x -> out
+//   compressor_meter_kernel     only for a node with the meter on: reduction() after every quantum (:304-306), a gather out of yL
 // The block constants (shifted threshold, knee_partial, the taus, the make-up gain) come from the host, per quantum (CompRow).
 //
 // Arithmetic.  The file is compiled like the rest of the library with -ffp-contract=off (Rust never fuses a * b + c) and
@@ -31,7 +32,9 @@ namespace waa {
 
 namespace {
 
-__device__ __forceinline__ const CompRow* comp_row(const CompDesc& d, uint32_t inst, uint64_t frame) {
+// (D: CompDesc, or the meter's CompMeterDesc — the same four fields)
+template <class D>
+__device__ __forceinline__ const CompRow* comp_row(const D& d, uint32_t inst, uint64_t frame) {
   const uint32_t q = min((uint32_t)(frame / RQ), d.n_quanta - 1u);
   return d.rows + (uint64_t)inst * d.row_inst_stride + (uint64_t)q * d.row_q_stride;
 }
@@ -218,6 +221,19 @@ __global__ __launch_bounds__(256) void compressor_apply_kernel(const CompDesc d)
   }
 }
 
+// ---- meter: reduction() after every quantum (:304-306) -----------------------------------------------------------------
+// The reference stores `-detector_value + makeup_gain` of a quantum's LAST frame when the quantum is done (:440, :450); with the
+// detector's yL of every frame still in the plane that is one f32 negation and one f32 add per (context, quantum), in the
+// reference's order.  grid (n_quanta / 256, n_inst), one thread per value: a 4-byte read at a 512-byte stride, a dense store.
+__global__ __launch_bounds__(256) void compressor_meter_kernel(const CompMeterDesc d) {
+  const uint32_t inst = blockIdx.y;
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= d.n_quanta) return;
+  const uint64_t last = (uint64_t)q * RQ + (RQ - 1);  // (< n_quanta * 128 <= frames)
+  const float yl = d.yl[(uint64_t)inst * d.frames + last];
+  d.out[(uint64_t)inst * d.n_quanta + q] = __fadd_rn(-yl, comp_row(d, inst, last)->makeup);
+}
+
 // level and apply have the instance on gridDim.y: a batch of more instances than a grid has rows goes in slices
 template <class L>
 static bool comp_sliced(const CompDesc& d, L&& launch) {
@@ -252,6 +268,22 @@ void launch_compressor_apply(const CompDesc& d, void* stream) {
   if (comp_sliced(d, [&](const CompDesc& s) { launch_compressor_apply(s, stream); })) return;
   const dim3 grid((uint32_t)((d.frames + 1023) / 1024), d.n_inst), block(256);
   hipLaunchKernelGGL(compressor_apply_kernel, grid, block, 0, (hipStream_t)stream, d);
+}
+
+void launch_compressor_meter(const CompMeterDesc& d, void* stream) {
+  if (d.n_inst > MAX_GRID_ROWS) {  // (whole contexts per slice, like level and apply)
+    for_grid_row_slices(d.n_inst, 1, [&](uint32_t first, uint32_t count) {
+      CompMeterDesc s = d;
+      advance_instances(s.yl, first, d.frames);
+      advance_instances(s.rows, first, d.row_inst_stride);
+      advance_instances(s.out, first, d.n_quanta);
+      s.n_inst = count;
+      launch_compressor_meter(s, stream);
+    });
+    return;
+  }
+  const dim3 grid((d.n_quanta + 255) / 256, d.n_inst), block(256);
+  hipLaunchKernelGGL(compressor_meter_kernel, grid, block, 0, (hipStream_t)stream, d);
 }
 
 }  // namespace waa

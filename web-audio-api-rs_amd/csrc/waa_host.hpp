@@ -272,6 +272,10 @@ struct Node {
   uint32_t an_series_pulls(uint32_t n_quanta) const {
     return an_series() && desc.i[2] >= 0 && (uint32_t)desc.i[2] <= n_quanta ? (n_quanta - (uint32_t)desc.i[2]) / (uint32_t)desc.i[1] + 1 : 0;
   }
+  // DynamicsCompressorNode with the meter on (desc.i[0] = 1): reduction() after every quantum, [n_inst][n_quanta] on the device,
+  // allocated by plan_compressor and written by every render (compressor_meter_kernel)
+  float* d_comp_red = nullptr;
+  bool comp_meter() const { return desc.kind == WAA_NODE_DYNAMICS_COMPRESSOR && desc.i[0] == 1; }
   float* d_window = nullptr;
   Cplx *d_an_tw = nullptr, *d_an_twfull = nullptr;
   float *d_an_prev = nullptr, *d_an_db = nullptr, *d_an_time = nullptr;
@@ -422,6 +426,10 @@ struct Step {
   RouteDesc route{};      // Route: ChannelMergerNode / the input bus of a ChannelSplitterNode (waa_route.hip; reads / writes in loop_reads / loop_writes)
   CompDesc comp{};        // Compressor (profile slots: slot_fwd = level, slot_mac = detector, slot_inv = apply)
   ShaperInstDesc shaper{};  // ShaperInst
+  // Compressor of a node with the meter on (desc.i[0] = 1): the fourth launch of the step, behind apply (meter.out != nullptr;
+  // profile slot: slot_meter).  It is part of the node's step, so nothing can be ordered between it and the detector.
+  CompMeterDesc meter{};
+  int slot_meter = -1;
   int slot_fwd = -1, slot_mac = -1, slot_inv = -1;
   void* zero_ptr = nullptr;
   size_t zero_bytes = 0;

@@ -268,6 +268,18 @@ struct CompDesc {
 void launch_compressor_level(const CompDesc& d, void* stream);
 void launch_compressor_detector(const CompDesc& d, void* stream);
 void launch_compressor_apply(const CompDesc& d, void* stream);
+// DynamicsCompressorNode::reduction() (dynamics_compressor.rs:304-306: the value stored at :440 / :450 after every quantum) of a
+// node created with the meter on (waa_node_desc.i[0] = 1): a fourth launch behind the three, one gather out of the yL plane.
+// A descriptor of its own: CompDesc is the kernel argument of the three kernels above and stays as it is.
+struct CompMeterDesc {
+  const float* yl;         // CompDesc::xl after the detector: [n_inst][frames]
+  const CompRow* rows;     // as CompDesc::rows
+  uint32_t row_inst_stride, row_q_stride;
+  float* out;              // [n_inst][n_quanta]: out[inst][q] = -yL[inst][128 q + 127] + makeup(inst, q)
+  uint32_t n_inst, n_quanta;
+  uint64_t frames;
+};
+void launch_compressor_meter(const CompMeterDesc& d, void* stream);
 
 // ---- WaveShaperNode with one curve per instance (waa_waveshaper_set_curve_instance), node-major in one launch (waa_shaper_inst.hip) ----
 // The curves of a node are one pool of floats, one row per DISTINCT curve; a row starts on a 16-byte boundary and the pool is

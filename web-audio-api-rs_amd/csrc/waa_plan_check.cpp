@@ -68,6 +68,7 @@ static StepIo step_io_raw(const Step& st) {
     case StepKind::Compressor:
       io.reads.push_back(st.comp.in.base);
       io.writes.push_back(st.comp.out.base);
+      if (st.meter.out) io.writes.push_back(st.meter.out);  // (the reduction trace: read by the getters alone)
       break;
     case StepKind::ShaperInst:
       io.reads.push_back(st.shaper.in.base);

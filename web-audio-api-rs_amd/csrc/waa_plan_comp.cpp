@@ -97,6 +97,22 @@ int plan_compressor(waa_batch* b, uint32_t id) {
   st.slot_fwd = slot_for(b, "compressor_level_kernel");
   st.slot_mac = slot_for(b, "compressor_detector_kernel");
   st.slot_inv = slot_for(b, "compressor_apply_kernel");
+  if (n.comp_meter()) {
+    // reduction() after every quantum (dynamics_compressor.rs:304-306, stored at :440 / :450): the detector leaves yL of every
+    // frame in `xl`, the make-up gain of every (context, quantum) is in the rows — one gather launch behind apply.  The buffer
+    // belongs to the plan: a re-armed batch renders a fresh trace into it.
+    if ((e = dev_alloc(b, &n.d_comp_red, (size_t)b->n_inst * b->n_quanta))) return e;
+    CompMeterDesc& m = st.meter;
+    m.yl = xl;
+    m.rows = d_rows;
+    m.row_inst_stride = d.row_inst_stride;
+    m.row_q_stride = d.row_q_stride;
+    m.out = n.d_comp_red;
+    m.n_inst = b->n_inst;
+    m.n_quanta = b->n_quanta;
+    m.frames = b->lp;
+    st.slot_meter = slot_for(b, "compressor_meter_kernel");
+  }
   b->steps.push_back(st);
   plan_note(b, "compressor node %u: %dch, look-ahead %u quanta, %u x %u row(s) of block constants (%s, %s) -> compressor_level_kernel, "
                "compressor_detector_kernel (%u wavefront(s), one lane per context), compressor_apply_kernel; first row: threshold=%g knee=%g "
@@ -104,6 +120,7 @@ int plan_compressor(waa_batch* b, uint32_t id) {
             id, d.nch, d.delay_frames / (uint32_t)RQ, n_rows_inst, n_rows_q, shared ? "shared" : "per instance",
             varies ? "per quantum" : "constant", (b->n_inst + 63) / 64, (double)pv[0][0], (double)pv[1][0], (double)pv[2][0], (double)pv[3][0],
             (double)pv[4][0]);
+  if (n.comp_meter()) plan_note(b, "compressor node %u: reduction trace, %u x %u values -> compressor_meter_kernel", id, b->n_inst, b->n_quanta);
   return 0;
 }
 

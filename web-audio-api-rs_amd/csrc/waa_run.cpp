@@ -86,7 +86,8 @@ static int run_step(waa_batch* b, const Step& st, uint32_t t0, uint32_t t1) {
     case StepKind::Compressor:  // (never inside a feedback loop: always the whole render)
       if (int e = launch_whole(b, st.slot_fwd, st.comp, launch_compressor_level)) return e;
       if (int e = launch_whole(b, st.slot_mac, st.comp, launch_compressor_detector)) return e;
-      return launch_whole(b, st.slot_inv, st.comp, launch_compressor_apply);
+      if (int e = launch_whole(b, st.slot_inv, st.comp, launch_compressor_apply)) return e;
+      return st.meter.out ? launch_whole(b, st.slot_meter, st.meter, launch_compressor_meter) : 0;  // (the meter is opt-in: desc.i[0])
     case StepKind::Route: return launch_whole(b, slot, st.route, launch_route);  // (never inside a feedback loop)
     case StepKind::ShaperInst: return launch_whole(b, slot, st.shaper, launch_shaper_inst);  // (never inside a feedback loop: the whole render)
   }

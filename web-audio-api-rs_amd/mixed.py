@@ -56,6 +56,8 @@ def _node_key(nd) -> tuple:
     if isinstance(nd, OscillatorNode) and nd.context._b.prefix == "waa_" and nd.type_of(0) != "custom":
         # ... and one built-in oscillator type per context; a context with a PeriodicWave stays apart from one without (below)
         ints = ("oscillator-type",) + ints[1:]
+    # (a DynamicsCompressorNode's meter is i[0] and stays in the key: a metered context and an unmetered one are two plans — the
+    # second has no trace buffer and no fourth launch — and do not merge)
     dbls = tuple(float(x) for x in d.d)
     if isinstance(nd, PannerNode) and nd.context._b.prefix == "waa_":
         # ... and one set of distance and cone options per context (i[1], d[0..5]); the panning model (i[0]) stays in the key
