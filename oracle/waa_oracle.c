@@ -2429,7 +2429,9 @@ uint64_t orc_buffer_resample(const float* src, uint64_t frames, float source_sr,
     double position = (double)i / (double)(tl - 1);
     double playhead = position * (double)(frames - 1);
     double pf = floor(playhead);
-    uint64_t prev = (uint64_t)pf;
+    /* a target length of 1 makes position 0 / 0: Rust's `as usize` turns the NaN playhead into index 0 (a saturating
+     * cast; in C the conversion of a NaN is undefined), k stays NaN and the one sample emitted is NaN */
+    uint64_t prev = pf == pf ? (uint64_t)pf : 0;
     uint64_t next = prev + 1 < frames - 1 ? prev + 1 : frames - 1;
     float k = (float)(playhead - pf);
     float kinv = 1.f - k;

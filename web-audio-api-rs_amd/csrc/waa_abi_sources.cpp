@@ -245,7 +245,9 @@ uint64_t waa_buffer_resample(const float* src, uint64_t frames, float source_sr,
     const double position = (double)i / (double)(tl - 1);
     const double playhead = position * (double)(frames - 1);
     const double pf = std::floor(playhead);
-    const uint64_t prev = (uint64_t)pf;
+    // a target length of 1 makes position 0 / 0: Rust's `as usize` turns the NaN playhead into index 0 (a saturating cast; in
+    // C++ the conversion of a NaN is undefined), k stays NaN and the one sample emitted is NaN
+    const uint64_t prev = pf == pf ? (uint64_t)pf : 0;
     const uint64_t next = std::min<uint64_t>(prev + 1, frames - 1);
     const float k = (float)(playhead - pf), kinv = 1.f - k;
     dst[i] = kinv * src[prev] + k * src[next];

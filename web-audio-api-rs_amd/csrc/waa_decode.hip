@@ -26,7 +26,7 @@ __device__ __forceinline__ void pcm16_resample_item(const DecodeDesc& d, uint32_
     const double position = (double)i / (double)(d.target_frames - 1);  // [0, 1]
     const double playhead = position * (double)(d.frames - 1);
     const double pf = floor(playhead);
-    prev = (uint64_t)pf;
+    prev = pf == pf ? (uint64_t)pf : 0;  // (target length 1: position is 0 / 0; the reference's `as usize` makes the NaN index 0)
     next = prev + 1 < d.frames - 1 ? prev + 1 : d.frames - 1;
     k = (float)(playhead - pf);
   }
