@@ -187,6 +187,55 @@ waa_status waa_panner_set_options_instance(waa_batch* batch, uint32_t node, uint
 waa_status waa_compressor_get_reduction(waa_batch* batch, uint32_t node, uint32_t instance, float* value);
 waa_status waa_compressor_get_reduction_series(waa_batch* batch, uint32_t node, float* dst, uint32_t n_quanta);
 
+/* Levels of the rendered output, computed on the device where the audio lies (the reference hands back f32 planes and nothing
+ * else: this is an extension, like waa_download_all_pcm16 and the reduction trace).  Answers, without the f32 download: did a
+ * context go non-finite and where, how loud is it overall and over time, how many samples will waa_download_all_pcm16 saturate.
+ *
+ * A ROW is one (instance i, output channel c): what waa_download(b, i, c, ...) returns, L = length_frames samples in
+ * n_q = ceil(L / 128) render quanta; a channel the destination's signal does not carry is a row of zeros.  Every value is defined
+ * on the sample's 32 bits, a = bits & 0x7fffffff, e = a >> 23 (e == 255: non-finite; e == 0: zero or denormal), so that nothing
+ * depends on what a convert or a compare does with a denormal, and it is exact: a model reproduces it bit for bit
+ * (tests/levels_model.py).
+ *
+ *   p_q  per-quantum peak: the f32 whose bits are the unsigned maximum of `a` over the quantum's frames f < L with e != 255
+ *        (a denormal counts with its own bits); 0 when there is none.
+ *   e_q  per-quantum energy, f64: s_j = (double)x_j * (double)x_j (exact) for the frames f = 128 q + j < L with 1 <= e <= 254,
+ *        +0.0 otherwise; summed by the adjacent-pairs tree in index order (t0[k] = s[2k] + s[2k+1], t1[k] = t0[2k] + t0[2k+1],
+ *        ... seven levels), every add f64 round-to-nearest.
+ *   peak             max of p_q.
+ *   sum_sq           the quanta in blocks of 64 consecutive ones (a missing quantum is +0.0); b_m = the same tree over the block's
+ *                    64 e_q (six levels); sum_sq = (...((0.0 + b_0) + b_1) + ...), ascending.
+ *   n_nonfinite      frames < L with e == 255;  first_nonfinite: the smallest such frame, UINT64_MAX if none.
+ *   n_clipped        frames < L with e != 255 whose f32 product v = x * 32768.f has v > 32767.f or v < -32768.f: the samples
+ *                    the clamp of waa_download_all_pcm16 changes (1.0f counts; -1.0f and 32767/32768 do not; a finite x whose
+ *                    product overflows to infinity counts).
+ * Nothing depends on the grid, the batch size, a row's neighbours or the run; there are no floating-point atomics.
+ *
+ * waa_output_levels: out[n_instances][n_channels_out].  waa_output_level_series: p_q and e_q, [n_instances][n_channels_out]
+ * [n_quanta] each; either pointer may be NULL, not both.  Both compute from the output as it lies on the device when they are
+ * called (nothing is cached: after waa_batch_rearm and a new render they give the new render's values) and wait for the render
+ * as waa_download_all does.  The workspace (12 bytes per row and quantum, plus 40 per row and 64-quantum block) is allocated on
+ * the first call and freed with the batch; a failed allocation is the call's status.  length_frames == 0: WAA_OK, nothing written.
+ *
+ * waa_download_all_pcm16_gain: waa_download_all_pcm16 with v = x * gain[instance] (one f32 multiply, unfused) in front of the
+ * packer's * 32768, clamp, NaN -> 0 and round to nearest even; gain[n_instances] in host memory.  gain[i] == 1 for every i gives
+ * the bits of waa_download_all_pcm16.
+ *
+ * Refusals, in this order: a NULL batch or pointer (WAA_ERR_INVALID_ARGUMENT); a plan-only batch (WAA_ERR_DEVICE); nothing
+ * rendered yet, and a ranged render (waa_render_range) in front of its last range (WAA_ERR_INVALID_STATE, InvalidStateError); a
+ * non-finite gain[i] (WAA_ERR_INVALID_ARGUMENT, naming the instance).
+ * Out of scope: levels of a node other than the destination, loudness weighting, batches merged from single
+ * contexts and waa_render_sharded (a `pull` callback may call these functions on its sub-batch). */
+typedef struct waa_level_stats {      /* 40 bytes, one per (instance, output channel) */
+  double   sum_sq;
+  uint64_t n_nonfinite, first_nonfinite, n_clipped;
+  float    peak;
+  uint32_t reserved;                  /* 0 */
+} waa_level_stats;
+waa_status waa_output_levels(waa_batch* batch, waa_level_stats* out);
+waa_status waa_output_level_series(waa_batch* batch, float* peak, double* sum_sq);
+waa_status waa_download_all_pcm16_gain(waa_batch* batch, int16_t* dst, const float* gain);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,7 +212,20 @@ ABI_DEVICE = {
     "panner_set_options_instance": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _VP]),
     "compressor_get_reduction": (C.c_int32, [_VP, C.c_uint32, C.c_uint32, _FP]),
     "compressor_get_reduction_series": (C.c_int32, [_VP, C.c_uint32, _FP, C.c_uint32]),
+    "output_levels": (C.c_int32, [_VP, _VP]),
+    "output_level_series": (C.c_int32, [_VP, _FP, _DP]),
+    "download_all_pcm16_gain": (C.c_int32, [_VP, C.POINTER(C.c_int16), _FP]),
 }
+
+
+class LevelStats(C.Structure):  # waa_level_stats (include/waa_hip_device.h): one per (instance, output channel)
+    _fields_ = [("sum_sq", C.c_double), ("n_nonfinite", C.c_uint64), ("first_nonfinite", C.c_uint64), ("n_clipped", C.c_uint64),
+                ("peak", C.c_float), ("reserved", C.c_uint32)]
+
+
+# the same 40 bytes as a numpy record (OfflineAudioContext.output_levels)
+LEVEL_STATS_DTYPE = np.dtype([("sum_sq", np.float64), ("n_nonfinite", np.uint64), ("first_nonfinite", np.uint64), ("n_clipped", np.uint64),
+                              ("peak", np.float32), ("reserved", np.uint32)])
 
 
 class PannerOptions(C.Structure):  # waa_panner_options (include/waa_hip_device.h)
@@ -2011,6 +2024,55 @@ class OfflineAudioContext:
         for k, inst in enumerate(instances):
             for c in range(self.number_of_channels):
                 self._b.check(self._b.download(self._handle, int(inst), c, _fp(out[k, c]), self.length))
+        return out
+
+    # -- levels of the rendered output, computed on the device (include/waa_hip_device.h: waa_output_levels & co.) --------------
+    def _rendered_on_device(self, what):
+        if self._b.prefix != "waa_":
+            raise WaaError(4, f"{what} is a feature of the device library; this binding hands back f32 planes and nothing else")
+        if self._handle is None or not self._rendered or self._now_q > 0:
+            raise WaaError(3, "InvalidStateError - nothing rendered yet")
+
+    def output_levels(self) -> np.ndarray:
+        """[n_instances, n_channels] records with the fields sum_sq (f64), n_nonfinite, first_nonfinite, n_clipped (u64) and peak
+        (f32) of every context's every output channel, as waa_hip_device.h defines them — without downloading the audio.  After
+        start_rendering_sync or render_async, until close()."""
+        self._rendered_on_device("output_levels")
+        out = np.zeros((self.n_instances, self.number_of_channels), LEVEL_STATS_DTYPE)
+        out["first_nonfinite"] = np.iinfo(np.uint64).max  # (a context of no frames: the library writes nothing)
+        self._b.check(self._b.output_levels(self._handle, out.ctypes.data_as(_VP)))
+        return out[["sum_sq", "n_nonfinite", "first_nonfinite", "n_clipped", "peak"]]
+
+    def output_level_series(self):
+        """(peak float32, sum_sq float64), each [n_instances, n_channels, n_quanta]: the peak and the energy of every render quantum
+        of every output channel"""
+        self._rendered_on_device("output_level_series")
+        shape = (self.n_instances, self.number_of_channels, (self.length + RENDER_QUANTUM_SIZE - 1) // RENDER_QUANTUM_SIZE)
+        peak, sum_sq = np.zeros(shape, np.float32), np.zeros(shape, np.float64)
+        self._b.check(self._b.output_level_series(self._handle, _fp(peak), sum_sq.ctypes.data_as(_DP)))
+        return peak, sum_sq
+
+    def download_pcm16(self, gain=None, normalize_peak=None) -> np.ndarray:
+        """int16 [n_instances, length, n_channels]: every context's AudioBuffer as interleaved 16-bit PCM (sample * 32768, rounded to
+        nearest even, saturated, NaN -> 0).  gain: [n_instances], each context multiplied by its own (one f32 multiply) in front of
+        the pack.  normalize_peak=t: gain[i] = float32(t) / (the largest peak of context i's channels), computed on the host from
+        output_levels(); 1 for a silent context.  Giving both is a ValueError."""
+        if gain is not None and normalize_peak is not None:
+            raise ValueError("download_pcm16: give gain or normalize_peak, not both")
+        self._rendered_on_device("download_pcm16")
+        if normalize_peak is not None:
+            peak = self.output_levels()["peak"].max(axis=1).astype(np.float32)
+            gain = np.ones(self.n_instances, np.float32)
+            np.divide(np.float32(normalize_peak), peak, out=gain, where=peak > 0)
+        out = np.empty((self.n_instances, self.length, self.number_of_channels), np.int16)
+        dst = out.ctypes.data_as(C.POINTER(C.c_int16))
+        if gain is None:
+            self._b.check(self._b.download_all_pcm16(self._handle, dst))
+            return out
+        gain = _f32(gain)
+        if gain.shape != (self.n_instances,):
+            raise ValueError(f"gain: expected {self.n_instances} values, one per context (got shape {gain.shape})")
+        self._b.check(self._b.download_all_pcm16_gain(self._handle, dst, _fp(gain)))
         return out
 
     def plan_describe(self) -> str:

@@ -893,6 +893,33 @@ struct EncodeDesc {
 };
 void launch_pcm16_pack(const EncodeDesc& d, void* stream);
 
+// ---- levels of the rendered output (waa_levels.hip; waa_output_levels & co. of include/waa_hip_device.h) ----
+// A row is one (item, output channel); a channel >= nch_in is a row of zeros.  LevelRec is waa_level_stats field for field (the
+// host glue asserts it): the record of a row, and of one 64-quantum block of a row (sum_sq = the block's tree b_m).
+struct LevelRec {
+  double sum_sq;
+  uint64_t n_nonfinite, first_nonfinite, n_clipped;
+  uint32_t peak_bits, reserved;
+};
+constexpr uint32_t LEVEL_BLOCK_QUANTA = 64;
+struct LevelsDesc {
+  const float* in;           // planes: in[item * in_item_stride + ch * in_ch_stride + frame]
+  uint64_t frames, in_item_stride, in_ch_stride;
+  uint32_t nch_in, nch_out, n_items, n_quanta;
+  uint32_t n_blocks, pad;    // ceil(n_quanta / 64)
+  double* q_sum_sq;          // [rows][n_quanta] e_q
+  uint32_t* q_peak;          // [rows][n_quanta] bits of p_q
+  LevelRec* blocks;          // [rows][n_blocks]
+  LevelRec* rows;            // [rows]
+};
+void launch_output_levels(const LevelsDesc& d, void* stream);       // per-quantum values and block records
+void launch_output_level_rows(const LevelsDesc& d, void* stream);   // block records -> row records
+struct EncodeGainDesc {
+  EncodeDesc e;
+  const float* gain;         // [n_items] on the device
+};
+void launch_pcm16_pack_gain(const EncodeGainDesc& d, void* stream);
+
 // launchers implemented in waa_kernels.hip
 void launch_chain(const ChainDesc& d, int cmax, void* stream);
 // the echo loop with its delay line in LDS (waa_echo.hip): qualification (delay range in frames over all instances) and launch
