@@ -236,6 +236,62 @@ waa_status waa_output_levels(waa_batch* batch, waa_level_stats* out);
 waa_status waa_output_level_series(waa_batch* batch, float* peak, double* sum_sq);
 waa_status waa_download_all_pcm16_gain(waa_batch* batch, int16_t* dst, const float* gain);
 
+/* Integrated loudness (ITU-R BS.1770-4 / EBU R 128) of every context's rendered output, computed on the device where the audio
+ * lies: an extension like the levels above, and what a data-set pipeline normalises to (-23 LUFS, -16, -14) in front of
+ * waa_download_all_pcm16_gain.  The device computes the K-weighted energy of every 100 ms sub-block of every row; blocks, gates and
+ * logarithms are host arithmetic on those few doubles, the same code for every source of them (waa_loudness_from_series).
+ *
+ * Sub-blocks.  A ROW is one (instance, output channel) of L = length_frames frames at sample rate sr.  h = floor(sr / 10 + 0.5)
+ *   frames are one sub-block (waa_loudness_hop), n_sub = floor(L / h); frames past n_sub * h belong to no block and are not read.
+ * Samples, decided on the bits as above: e == 255 (non-finite) and e == 0 (zero, denormal) enter as +0.0, every other sample as
+ *   (double)x; a channel the destination's signal does not carry is a row of zeros.
+ * K-weighting: two biquads in f64, coefficients computed on the host in f64 from sr.
+ *   Stage 1, the shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / sr),
+ *     Vh = 10^(G / 20), Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2;
+ *     b0 = (Vh + Vb K / Q + K^2) / a0, b1 = 2 (K^2 - Vh) / a0, b2 = (Vh - Vb K / Q + K^2) / a0,
+ *     a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0.
+ *   Stage 2, the high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773; b = (1, -2, 1), not divided by a0; a1, a2 as above.
+ *   (At 48 kHz these are the tables of BS.1770-4 to 1e-15.)
+ *   Each stage is transposed direct form II, unfused, in this order: v = b0 x + p1;  p1 = (b1 x - a1 v) + p2;  p2 = b2 x - a2 v.
+ *   Stage 2 runs on v with its own state (q1, q2) and gives w.  The state is zero at frame 0.
+ * Sub-block energy: z[j] = (...((0 + w_0^2) + w_1^2) + ...) over the sub-block's h frames, ascending, f64.
+ *   The device computes z in three launches (a zero-state pass per sub-block, a chain over the sub-blocks' states, an exact pass
+ *   from the handed-over state), so z is the serial recurrence's value up to the rounding of the hand-over — DESIGN.md 3.14 and
+ *   tests/loudness_model.py derive the bound, below 1e-9 of z on ordinary signals — and the same bits whatever the batch, the grid and the run.
+ *   A row of zeros gives exact zeros.
+ * Channel weights G_c: weights[n_channels_out] if given (finite, >= 0); otherwise by the Web Audio layouts — six channels
+ *   (1, 1, 1, 0, 1.41, 1.41), four channels (1, 1, 1.41, 1.41), anything else 1 per channel.
+ * Blocks: block k covers sub-blocks k .. k + 3, k = 0 .. n_sub - 4;  P_k = sum_c G_c (z_c[k] + z_c[k+1] + z_c[k+2] + z_c[k+3])
+ *   / (4 h);  l_k = -0.691 + 10 log10 P_k, -inf for P_k = 0.
+ * integrated: A = the blocks with l_k > -70;  relative_threshold = -0.691 + 10 log10(mean_A P_k) - 10 (-inf when A is empty);
+ *   B = the blocks of A with l_k > relative_threshold;  integrated = -0.691 + 10 log10(mean_B P_k), -inf when B is empty (a clip
+ *   shorter than 400 ms is one such case).  Means are ascending f64 sums.
+ * momentary_max = max l_k.  short_term_max: the same formula over windows of 30 sub-blocks, hop one sub-block, ungated; -inf when
+ *   n_sub < 30.  n_blocks = max(n_sub - 3, 0), n_gated = |B|.
+ *
+ * waa_output_loudness: out[n_instances]; weights may be NULL.  waa_output_loudness_series: z[n_instances][n_channels_out][n_sub].
+ * Both compute from the output as it lies on the device when they are called (nothing is cached) and wait for the render as
+ * waa_download_all does.  The workspace (4 + 4 + 1 doubles per row and sub-block) is the batch's own, allocated on the first call
+ * and freed with the batch; a failed allocation is the call's status.  length_frames < h: WAA_OK, every field -inf / 0, no z written.
+ * waa_loudness_hop: h of a sample rate.
+ * waa_loudness_from_series: the blocks, gates and maxima of ONE context from its z[n_channels][n_sub] in host memory — no batch, no
+ * device; the code waa_output_loudness gates with.  For jobs that hold z from elsewhere: a `pull` callback of waa_render_sharded,
+ * contexts rendered one by one.  A NULL z (with something to read) or out, hop == 0 and a bad weight are WAA_ERR_INVALID_ARGUMENT.
+ *
+ * Refusals of the two batch calls, in this order: those of waa_output_levels, in its order and wording; then a negative or
+ * non-finite weight (WAA_ERR_INVALID_ARGUMENT, naming the channel).
+ * Out of scope: true peak, loudness range, dual-mono, batches merged from single contexts and
+ * waa_render_sharded (beyond what waa_loudness_from_series allows in a `pull` callback). */
+typedef struct waa_loudness_stats {   /* 40 bytes, one per instance */
+  double   integrated, momentary_max, short_term_max, relative_threshold;   /* LUFS */
+  uint32_t n_blocks, n_gated;
+} waa_loudness_stats;
+waa_status waa_output_loudness(waa_batch* batch, const double* weights /* NULL: default */, waa_loudness_stats* out);
+waa_status waa_output_loudness_series(waa_batch* batch, double* z);
+uint32_t waa_loudness_hop(double sample_rate);
+waa_status waa_loudness_from_series(const double* z, uint32_t n_channels, uint32_t n_sub, uint32_t hop, const double* weights,
+                                    waa_loudness_stats* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -215,6 +215,10 @@ ABI_DEVICE = {
     "output_levels": (C.c_int32, [_VP, _VP]),
     "output_level_series": (C.c_int32, [_VP, _FP, _DP]),
     "download_all_pcm16_gain": (C.c_int32, [_VP, C.POINTER(C.c_int16), _FP]),
+    "output_loudness": (C.c_int32, [_VP, _DP, _VP]),
+    "output_loudness_series": (C.c_int32, [_VP, _DP]),
+    "loudness_hop": (C.c_uint32, [C.c_double]),
+    "loudness_from_series": (C.c_int32, [_DP, C.c_uint32, C.c_uint32, C.c_uint32, _DP, _VP]),
 }
 
 
@@ -226,6 +230,44 @@ class LevelStats(C.Structure):  # waa_level_stats (include/waa_hip_device.h): on
 # the same 40 bytes as a numpy record (OfflineAudioContext.output_levels)
 LEVEL_STATS_DTYPE = np.dtype([("sum_sq", np.float64), ("n_nonfinite", np.uint64), ("first_nonfinite", np.uint64), ("n_clipped", np.uint64),
                               ("peak", np.float32), ("reserved", np.uint32)])
+
+
+class LoudnessStats(C.Structure):  # waa_loudness_stats (include/waa_hip_device.h): one per instance
+    _fields_ = [("integrated", C.c_double), ("momentary_max", C.c_double), ("short_term_max", C.c_double),
+                ("relative_threshold", C.c_double), ("n_blocks", C.c_uint32), ("n_gated", C.c_uint32)]
+
+
+# the same 40 bytes as a numpy record (OfflineAudioContext.output_loudness)
+LOUDNESS_STATS_DTYPE = np.dtype([("integrated", np.float64), ("momentary_max", np.float64), ("short_term_max", np.float64),
+                                 ("relative_threshold", np.float64), ("n_blocks", np.uint32), ("n_gated", np.uint32)])
+
+
+def _weights_arg(weights, n_channels):
+    """(array kept alive, pointer or None) for a `const double* weights` argument"""
+    if weights is None:
+        return None, None
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (n_channels,):
+        raise ValueError(f"weights: expected {n_channels} values, one per channel (got shape {w.shape})")
+    return w, w.ctypes.data_as(_DP)
+
+
+def loudness_from_series(z, hop, weights=None, binding=None) -> np.ndarray:
+    """waa_loudness_from_series: the loudness record (LOUDNESS_STATS_DTYPE, shape ()) of ONE context from its sub-block energies
+    z[n_channels, n_sub] and the sub-block's length in frames — host arithmetic, no batch and no device."""
+    if binding is None:
+        from . import default_binding  # loads libwaa_hip.so; raises if it is not built
+        binding = default_binding()
+    b = binding
+    if b.prefix != "waa_":
+        raise WaaError(4, "loudness_from_series is a feature of the device library; this binding hands back f32 planes and nothing else")
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    if z.ndim != 2:
+        raise ValueError(f"z: expected [n_channels, n_sub] (got shape {z.shape})")
+    w, wp = _weights_arg(weights, z.shape[0])
+    out = np.zeros((), LOUDNESS_STATS_DTYPE)
+    b.check(b.loudness_from_series(z.ctypes.data_as(_DP), z.shape[0], z.shape[1], int(hop), wp, out.ctypes.data_as(_VP)))
+    return out
 
 
 class PannerOptions(C.Structure):  # waa_panner_options (include/waa_hip_device.h)
@@ -2052,14 +2094,50 @@ class OfflineAudioContext:
         self._b.check(self._b.output_level_series(self._handle, _fp(peak), sum_sq.ctypes.data_as(_DP)))
         return peak, sum_sq
 
-    def download_pcm16(self, gain=None, normalize_peak=None) -> np.ndarray:
+    # -- integrated loudness of the rendered output (include/waa_hip_device.h: waa_output_loudness & co.) -----------------------
+    def output_loudness(self, weights=None) -> np.ndarray:
+        """[n_instances] records with the fields integrated, momentary_max, short_term_max, relative_threshold (LUFS, f64; -inf where
+        there is nothing to measure), n_blocks and n_gated of every context (BS.1770-4 as waa_hip_device.h defines it) — without
+        downloading the audio.  weights: one per output channel; None: the Web Audio layouts' (5.1 and quad surrounds 1.41, LFE 0)."""
+        self._rendered_on_device("output_loudness")
+        w, wp = _weights_arg(weights, self.number_of_channels)
+        out = np.zeros(self.n_instances, LOUDNESS_STATS_DTYPE)
+        self._b.check(self._b.output_loudness(self._handle, wp, out.ctypes.data_as(_VP)))
+        return out
+
+    def output_loudness_series(self) -> np.ndarray:
+        """float64 [n_instances, n_channels, n_sub]: the K-weighted energy of every whole 100 ms sub-block of every output channel"""
+        self._rendered_on_device("output_loudness_series")
+        hop = int(self._b.loudness_hop(self.sample_rate))
+        z = np.zeros((self.n_instances, self.number_of_channels, self.length // hop if hop else 0), np.float64)
+        self._b.check(self._b.output_loudness_series(self._handle, z.ctypes.data_as(_DP)))
+        return z
+
+    def download_pcm16(self, gain=None, normalize_peak=None, normalize_loudness=None, max_peak=None) -> np.ndarray:
         """int16 [n_instances, length, n_channels]: every context's AudioBuffer as interleaved 16-bit PCM (sample * 32768, rounded to
         nearest even, saturated, NaN -> 0).  gain: [n_instances], each context multiplied by its own (one f32 multiply) in front of
         the pack.  normalize_peak=t: gain[i] = float32(t) / (the largest peak of context i's channels), computed on the host from
-        output_levels(); 1 for a silent context.  Giving both is a ValueError."""
+        output_levels(); 1 for a silent context.  Giving both is a ValueError.  normalize_loudness=T (LUFS): gain[i] =
+        float32(10 ** ((T - I_i) / 20)) with I_i the integrated loudness of output_loudness(), 1 where that is -inf; with max_peak=p
+        no larger than float32(p) / (the context's peak).  It excludes gain and normalize_peak; max_peak needs it."""
         if gain is not None and normalize_peak is not None:
             raise ValueError("download_pcm16: give gain or normalize_peak, not both")
+        if normalize_loudness is not None and (gain is not None or normalize_peak is not None):
+            raise ValueError("download_pcm16: give normalize_loudness or one of gain and normalize_peak, not both")
+        if max_peak is not None and normalize_loudness is None:
+            raise ValueError("download_pcm16: max_peak limits the gain of normalize_loudness and needs it")
         self._rendered_on_device("download_pcm16")
+        if normalize_loudness is not None:
+            integrated = self.output_loudness()["integrated"]
+            gain = np.ones(self.n_instances, np.float32)
+            measured = np.isfinite(integrated)
+            with np.errstate(over="ignore"):
+                gain[measured] = np.float32(10.0 ** ((float(normalize_loudness) - integrated[measured]) / 20.0))
+            if max_peak is not None:
+                peak = self.output_levels()["peak"].max(axis=1).astype(np.float32)
+                limit = np.full(self.n_instances, np.inf, np.float32)
+                np.divide(np.float32(max_peak), peak, out=limit, where=peak > 0)
+                gain = np.minimum(gain, limit)
         if normalize_peak is not None:
             peak = self.output_levels()["peak"].max(axis=1).astype(np.float32)
             gain = np.ones(self.n_instances, np.float32)

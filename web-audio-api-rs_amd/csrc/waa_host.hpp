@@ -562,6 +562,7 @@ struct waa_batch {
   int16_t* pcm_out = nullptr;     // staging of waa_download_all_pcm16 (allocated on first use, freed with the batch)
   size_t pcm_out_count = 0;
   void* levels_ws = nullptr;      // workspace of waa_output_levels / _level_series (waa_levels_host.cpp; first use, freed with the batch)
+  void* loudness_ws = nullptr;    // workspace of waa_output_loudness / _loudness_series (waa_loudness_host.cpp; likewise)
   float* pcm_gain = nullptr;      // [n_inst] the gains of waa_download_all_pcm16_gain on the device (likewise)
   bool dry = false;                  // WAA_DEVICE_PLAN_ONLY: allocations are host memory, nothing is launched
   std::vector<std::string> plan_log;  // waa_plan_describe

@@ -7,6 +7,7 @@
 
 #include "../../include/waa_hip_device.h"
 #include "waa_host.hpp"
+#include "waa_output_calls.hpp"
 
 static_assert(sizeof(waa_level_stats) == 40 && sizeof(waa::LevelRec) == 40, "one 40-byte record per row");
 static_assert(offsetof(waa_level_stats, sum_sq) == offsetof(waa::LevelRec, sum_sq) &&
@@ -18,27 +19,6 @@ static_assert(offsetof(waa_level_stats, sum_sq) == offsetof(waa::LevelRec, sum_s
               "the device's record is waa_level_stats");
 
 namespace {
-
-// the checks the three calls share, in the order and wording of waa_download_all_pcm16 and waa_download
-int check_rendered(waa_batch* b) {
-  if (b->dry) return fail(WAA_ERR_DEVICE, "plan-only batch has no device");
-  if (!b->planned || !b->rendered) return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - nothing rendered yet");
-  if (b->ranged && b->ctl_q < b->n_quanta)
-    return fail(WAA_ERR_INVALID_STATE, "InvalidStateError - a ranged render is in progress (suspended in front of quantum %u): the output is complete "
-                                       "once the last range is rendered", b->ctl_q);
-  return 0;
-}
-// a launch made at call time, like an analyser pull: it gets its profile slot when it is first made on a profiled batch, so the
-// profile of a batch that never asks for its levels lists what it always listed
-template <typename L>
-int call_launch(waa_batch* b, const char* name, L&& launch) {
-  return timed(b, b->profiling ? slot_for(b, name) : -1, launch);
-}
-int wait_for_render(waa_batch* b) {
-  HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  return settle_loops(b);
-}
 
 // both levels kernels over the destination's signal; *out describes where the results lie in the batch's workspace
 int run_levels(waa_batch* b, waa::LevelsDesc* out) {
